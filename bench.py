@@ -21,7 +21,10 @@ workload of BASELINE.md section 3: obs dim 32, 3 objectives, 6 actions, net [256
 (16 384 TD rows = 49 152 scalar TD errors per step), replay buffer pre-filled with 20 000 seeded transitions, PER on
 (the reference default).  The replay data is resident in HBM before the timed region starts; the per-step host work
 (index / weight sampling on the reference's RNG streams) is inside it.
-Prints ONE JSON line (rank 0).  ``value`` = TD-row updates per second of the whole job.
+Prints ONE JSON line (rank 0).  ``value`` = TD-row updates per second of the whole job.  ``--steps K`` is the number of timed
+steps of the headline job; ``ms_per_step`` is its wall time over them.  ``--dump-outputs DIR`` also writes what the headline job's
+last timed step computed (``step_outputs``: parameters, Adam moments, loss, gradient norm, priorities) as ``DIR/<name>.npy``,
+float32; every input is seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -327,10 +330,36 @@ def _clock_ramp(dev, seconds=0.5):
     del x
 
 
-def run_job(a, dist, world, rank, dev, W, sharded, steps, warmup, axis="batch", ramp=True, exact_f32=False):
+def step_outputs(agent):
+    """What the caller of ``Envelope.update()`` holds after the last timed step, as host float32 arrays: the online and target
+    parameters, Adam's two moments, the step's loss, and (PER) the new priorities of its sampled transitions.  ~3.4 MB at the
+    flagship shape."""
+    host = lambda t: t.detach().reshape(-1).to("cpu", th.float32).numpy()
+    out = {"params_online": host(agent.q_net.flat), "params_target": host(agent.target_q_net.flat),
+           "adam_exp_avg": host(agent._exp_avg), "adam_exp_avg_sq": host(agent._exp_avg_sq),
+           "loss": host(agent._losses[-1])}
+    for k in ("grad_norm", "priority"):
+        v = (agent._out or {}).get(k)
+        if v is not None:
+            out[k] = host(v)
+    return out
+
+
+def dump_outputs(outputs, out_dir, limit_bytes=64 << 20):
+    """``--dump-outputs DIR``: one ``DIR/<name>.npy`` per array."""
+    total = sum(v.nbytes for v in outputs.values())
+    if total > limit_bytes:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {limit_bytes} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def run_job(a, dist, world, rank, dev, W, sharded, steps, warmup, axis="batch", ramp=True, exact_f32=False, dump=False):
     """Build the agent for a job of W sampled weights in total, run warm-up + `steps` timed Envelope.update() steps bracketed
     by barrier + synchronize on both sides; returns the measurements (wall = max over ranks).  exact_f32: every GEMM on the
-    f32-input MFMA (morl_ctx_set_exact_f32: the "no split trick" leg of the line)."""
+    f32-input MFMA (morl_ctx_set_exact_f32: the "no split trick" leg of the line).  dump: also return what the last timed step
+    computed (``step_outputs``) under "outputs"."""
     from morl_baselines_amd.envelope import Envelope
 
     th.manual_seed(0)
@@ -416,6 +445,8 @@ def run_job(a, dist, world, rank, dev, W, sharded, steps, warmup, axis="batch", 
            "fwd_launches_per_step": kinds0["forward"][0], "fwd2_launches_per_step": kinds0["forward2"][0], "transport": transport, "comm_ranks": comm_ranks, "axis": axis if sharded else None,
            "lazy_target_rows": lazy_rows, "bf16": agent.q_net.ctx.last_step_bf16(),
            "loss": agent.last_loss(), "engine": agent.q_net.ctx.engine, "W": W, "B": B}
+    if dump:
+        res["outputs"] = step_outputs(agent)
     del agent
     return res
 
@@ -700,6 +731,10 @@ def main():
                     help="collectives of the N > 1 rank steps: auto = MORL_COMM, else RCCL inside libmorl_hip.so on an RCCL process group "
                          "(falling back, on every rank together, to the torch.distributed call-backs); staged = the library calls of a "
                          "rank step one by one with torch.distributed between them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline job's last timed step computed (rank 0: parameters, "
+                         "Adam moments, loss, priorities) as DIR/<name>.npy, float32; the inputs are seeded, so two builds "
+                         "run with the same arguments can be compared array for array")
     ap.add_argument("--buffer-fill", type=int, default=20_000, help="seeded transitions in the replay buffer (BASELINE.md s3: 20 000)")
     ap.add_argument("--cpu-emulator", action="store_true",
                     help="FUNCTIONAL check without a GPU (the CPU test-suite's end-to-end run of this script): the ranks run the "
@@ -708,6 +743,8 @@ def main():
     ap.add_argument("--force-shard", action="store_true",
                     help="run the weight-sharded step (RCCL collectives) even with one rank (path check on a 1-GPU box)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(_self_spawn(a.gpus, sys.argv[1:], result_out))
@@ -749,10 +786,12 @@ def main():
     if sharded and B % parts:
         raise SystemExit(f"--batch {B} must be divisible by the number of ranks")
 
-    def job(W, axis, ramp=True, steps=None, exact_f32=False):
-        """One measured job; every rank must reach the same verdict, so a failure is agreed on through an all-reduce."""
+    def job(W, axis, ramp=True, steps=None, exact_f32=False, headline=False):
+        """One measured job; every rank must reach the same verdict, so a failure is agreed on through an all-reduce.
+        headline: a job the line's headline may come from (it keeps its outputs for --dump-outputs)."""
         try:
-            res = run_job(a, dist, world, rank, dev, W, sharded, steps or a.steps, a.warmup, axis, ramp, exact_f32)
+            res = run_job(a, dist, world, rank, dev, W, sharded, steps or a.steps, a.warmup, axis, ramp, exact_f32,
+                          dump=headline and a.dump_outputs is not None and rank == 0)
         except Exception as exc:
             import traceback
             traceback.print_exc()
@@ -772,13 +811,13 @@ def main():
     if sharded:
         axes = ["batch", "weights"] if a.shard_axis == "auto" else [a.shard_axis]
         if a.scaling == "weak":
-            weak = job(a.weights * world, "weights" if a.shard_axis == "auto" else a.shard_axis)
+            weak = job(a.weights * world, "weights" if a.shard_axis == "auto" else a.shard_axis, headline=world > 1)
             if not a.no_sub_record:
                 for ax in axes:
-                    strong[ax] = job(a.weights, ax)
+                    strong[ax] = job(a.weights, ax, headline=world == 1)
         else:
             for ax in axes:
-                strong[ax] = job(a.weights, ax)
+                strong[ax] = job(a.weights, ax, headline=True)
             if world > 1 and not a.no_sub_record:
                 weak = job(a.weights * world, "weights" if a.shard_axis == "auto" else a.shard_axis)
     else:
@@ -786,7 +825,7 @@ def main():
             # the same run shape WITHOUT the clock ramp, measured first (the chip still idles from the set-up): BASELINE.md s3's
             # procedure as written; the headline below runs behind the ramp and says so in config.setup
             no_ramp = job(a.weights, None, ramp=False)
-        strong["single"] = job(a.weights, None)
+        strong["single"] = job(a.weights, None, headline=True)
         if not a.no_sustained_record:
             # the same job over a long run: the lazily selected row count grows over the first ~ 1 000 updates of a fresh agent
             # (1 193 -> 1 749 of 16 384 at the flagship shape), so a 20-step line flatters the target rows' launch
@@ -846,6 +885,8 @@ def main():
             raise SystemExit(f"the headline job failed: {head_res}")
         h = record(head_res, W_head, scaling)
         head_axis = head_res.get("axis")
+        if a.dump_outputs is not None:
+            dump_outputs(head_res["outputs"], a.dump_outputs)
         out = {
             "metric": "Envelope-Q TD updates/sec (batch x weights x obj = 256 x 64 x 3)",
             "value": h["value"],

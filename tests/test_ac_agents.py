@@ -531,8 +531,6 @@ def test_gpi_eval_with_64_weight_support(be):
     """BASELINE config 3: the GPI set of 64 weight vectors -- |M|^2 = 4096 critic rows per evaluated action, streamed
     through a batch-128 engine's workspace in chunks; must pick the action the oracle's dense evaluation picks."""
     lib, dev = be
-    if dev.type == "cpu":
-        pytest.skip("reference-sized networks run on the GPU only (the emulator is slow)")
     D, Ad, R, m = 11, 3, 3, 64                              # mo-hopper-v4 shapes
     env = BoxEnv(D=D, Ad=Ad)
     env.reward_space = momdp.BoxSpace(0.0, 1.0, (R,), 0)

@@ -165,8 +165,6 @@ def run_and_check_against_oracle(lib, dev, c):
 @pytest.mark.parametrize("c", AC_CASES, ids=lambda c: c.name)
 def test_update_matches_oracle_and_reference(be, c):
     lib, dev = be
-    if dev.type == "cpu" and max(c.arch) >= 256:
-        pytest.skip("reference-sized networks run on the GPU only (the emulator is slow)")
     eng, res, do_policy = run_and_check_against_oracle(lib, dev, c)
     rel = lambda a, b: abs(float(a) - float(b)) <= 1e-5 * max(abs(float(b)), 1e-3)  # noqa: E731
     # ---- against the fixture the unmodified reference produced --------------------------------------------------------
@@ -246,8 +244,6 @@ def test_wave_and_lds_tile_engines_agree(be, name):
     (each deterministic) summation orders: gradients agree to fp32 round-off, and each engine reproduces itself bit for bit."""
     lib, dev = be
     c = [x for x in AC_CASES if x.name == name][0]
-    if dev.type == "cpu" and max(c.arch) >= 256:
-        pytest.skip("reference-sized networks run on the GPU only")
     inp = make_inputs(c)
     runs = {}
     try:

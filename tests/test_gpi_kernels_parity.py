@@ -92,8 +92,6 @@ def run_and_check_against_oracle(lib, dev, c):
 @pytest.mark.parametrize("c", GPI_CASES, ids=lambda c: c.name)
 def test_update_actions_priorities(be, c):
     lib, dev = be
-    if dev.type == "cpu" and max(c.arch) >= 256:
-        pytest.skip("reference-sized networks run on the GPU only (the emulator is slow)")
     eng, inp, res = run_and_check_against_oracle(lib, dev, c)
     # ---- the fixture of the unmodified reference -------------------------------------------------------------------------
     g = load_golden(c)

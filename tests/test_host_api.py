@@ -264,8 +264,6 @@ def _dominated(nd, n, rng):
 @pytest.mark.parametrize("n_nd,n_d,dims", [(100, 500, 2), (300, 1500, 4)])
 def test_filter_pareto_known_front(be, n_nd, n_d, dims):
     lib, dev = be
-    if dev.type == "cpu" and n_nd > 100:
-        pytest.skip("large front only on the GPU (emulator is O(N^2) fibers)")
     rng = np.random.default_rng(0)
     nd = _unit_ball_positive(n_nd, dims, rng)
     d = _dominated(nd, n_d, rng)

@@ -2,7 +2,7 @@
 rows), observation / action / objective counts and hidden widths (multiples of 4 up to 256, one to four layers), through every
 MLP engine, against the oracle with the per-update parity contract of test_kernels_parity.py.  The fixtures pin the reference's
 shapes; this pins the edges between them -- partial row tiles, K padding of odd input widths, narrow / wide last layers, split
-counts of the weight-gradient jobs.  The emulator takes the three smallest cases, the GPU all of them."""
+counts of the weight-gradient jobs.  The emulator and the GPU both run every case."""
 import numpy as np
 import pytest
 
@@ -30,15 +30,12 @@ def _random_cases(n, seed=2024):
 
 
 FUZZ = _random_cases(30)
-SMALL = sorted(FUZZ, key=lambda c: c.B * c.W * sum(c.arch))[:3]
 
 
 @pytest.mark.parametrize("fused", [1, 0], ids=["fused", "perlayer"])
 @pytest.mark.parametrize("c", FUZZ, ids=lambda c: c.name)
 def test_random_shapes_match_the_oracle(be, c, fused):
     lib, dev, is_sim = be
-    if is_sim and c not in SMALL:
-        pytest.skip("the emulator runs the three smallest shapes; the rest need the GPU")
     inp = make_inputs(c)
     res, t = run_update(lib, dev, c, inp, fused=fused, hidden=True)
     o, online, m, v = run_oracle(c, inp)
@@ -79,14 +76,11 @@ def _random_ac_cases(n, seed=77):
 
 
 AC_FUZZ = _random_ac_cases(24)
-AC_SMALL = sorted(AC_FUZZ, key=lambda c: c.B * sum(c.arch))[:3]
 
 
 @pytest.mark.parametrize("c", AC_FUZZ, ids=lambda c: c.name)
 def test_random_actor_critic_shapes_match_the_oracle(ac_be, c):
     lib, dev = ac_be
-    if dev.type == "cpu" and c not in AC_SMALL:
-        pytest.skip("the emulator runs the three smallest shapes; the rest need the GPU")
     run_and_check_against_oracle(lib, dev, c)
 
 
@@ -113,12 +107,9 @@ def _random_gpi_cases(n, seed=909):
 
 
 GPI_FUZZ = _random_gpi_cases(16)
-GPI_SMALL = sorted(GPI_FUZZ, key=lambda c: c.B * c.n_support * sum(c.arch))[:2]
 
 
 @pytest.mark.parametrize("c", GPI_FUZZ, ids=lambda c: c.name)
 def test_random_gpi_shapes_match_the_oracle(gpi_be, c):
     lib, dev = gpi_be
-    if dev.type == "cpu" and c not in GPI_SMALL:
-        pytest.skip("the emulator runs the two smallest shapes; the rest need the GPU")
     gpi_check(lib, dev, c)

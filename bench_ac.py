@@ -2,7 +2,7 @@
 continuous) on one MI355X.  bench.py stays the north-star (Envelope) line the driver runs; this script measures the
 widened rows with the same conventions:
 
-    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench_ac.py --workload morld --gpus N --pop 64      # the population's learners are independent units: pop / N per
                                                                 # GPU, no data-path collective ("replicas only", weak scaling)
@@ -35,6 +35,7 @@ SHAPES = {  # obs dim, action dim, objectives of the environments BASELINE.json 
     "gpipd": dict(D=11, Ad=3, R=3, env="mo-hopper-v4"),
     "gpi": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (GPI-PD, discrete: 6 actions)"),
     "ens": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (GPI-PD Dyna model: one-hot action in, next-obs delta + reward out)"),
+    "pcn": dict(D=9, Ad=4, R=2, env="treasure-line (discrete head) / mo-hopper-v4 shapes 11-3-3 (continuous head)"),
 }
 ARCH = [256, 256]
 B = 128
@@ -345,6 +346,97 @@ def bench_ens(a):
     print(json.dumps(out), file=RESULT_OUT, flush=True)
 
 
+def bench_pcn(a):
+    """PCN (multi_policy/pcn/pcn.py): the ``num_model_updates = 50`` back-to-back ``update()`` calls of one training iteration
+    (pcn.py:458-459) at the reference's defaults -- batch 256, hidden 64 -- as ONE ``morl_pcn_update_n`` call, on the discrete and
+    the continuous head; next to it the same 50 updates as eager torch ops on the same GPU (tests/pcn_oracle.py moved to the
+    device: index the device table, forward, loss, autograd, ``th.optim.Adam``).  The two legs alternate, ``--steps`` loops per
+    timed window, five windows each; the figure is the median window."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ctypes as C
+
+    import pcn_oracle as po
+    from morl_baselines_amd.native import load_library
+
+    lib, dev = load_library(), th.device("cuda", 0)
+    n_upd, B, H, lr = 50, 256, 64, 1e-3
+    loops = max(1, a.steps)
+    heads = {}
+    for head, (D, R, A, cont) in (("discrete", (9, 2, 4, False)), ("continuous", (11, 3, 3, True))):
+        rng = np.random.default_rng(0)
+        aw = A if cont else 1
+        rows = 2000                                     # ~100 stored episodes of ~20 transitions (max_buffer_size = 100)
+        table = rng.standard_normal((rows, D + aw + R + 1)).astype(np.float32)
+        table[:, D:D + aw] = rng.uniform(-1, 1, (rows, aw)) if cont else rng.integers(0, A, (rows, 1))
+        table[:, -1] = rng.integers(1, 20, rows)
+        idx = rng.integers(0, rows, (n_upd, B)).astype(np.int32)
+        scaling = np.linspace(0.1, 0.02, R + 1).astype(np.float32)
+        th.manual_seed(0)
+        init = po.init_params(D, R, A, H)
+        table_d, idx_d, scaling_d = th.tensor(table).to(dev), th.tensor(idx).to(dev), th.tensor(scaling).to(dev)
+        idx_l = idx_d.long()
+
+        h = C.c_void_p()
+        lib.check(lib.lib.morl_pcn_create(C.byref(h), D, R, A, H, int(cont), B))
+        lib.check(lib.lib.morl_pcn_set_table(h, table_d.data_ptr(), rows, lib.stream_of(table_d)))
+        flat0 = th.cat([p.reshape(-1) for p in init]).to(dev)
+        state = dict(p=flat0.clone(), m=th.zeros_like(flat0), v=th.zeros_like(flat0), steps=0)
+        loss_d = th.zeros(n_upd, device=dev)
+        pred_d = th.zeros(B, A, device=dev)
+
+        def fused_loop():
+            lib.check(lib.lib.morl_pcn_update_n(h, state["p"].data_ptr(), state["m"].data_ptr(), state["v"].data_ptr(),
+                                                scaling_d.data_ptr(), n_upd, idx_d.data_ptr(), B, lr, state["steps"],
+                                                loss_d.data_ptr(), None, pred_d.data_ptr(), lib.stream_of(loss_d)))
+            state["steps"] += n_upd
+
+        learner = po.Learner(init, scaling, cont, lr=lr, device=dev)
+        eager_losses = []
+
+        def eager_loop():
+            eager_losses.clear()
+            for k in range(n_upd):
+                rows_k = table_d[idx_l[k]]
+                actions = rows_k[:, D:D + aw] if cont else rows_k[:, D].long()
+                l, _ = learner.update(rows_k[:, :D], actions, rows_k[:, D + aw:D + aw + R], rows_k[:, -1:])
+                eager_losses.append(l)
+
+        # same inputs, same start: the first loop of each leg must agree before anything is timed
+        fused_loop()
+        eager_loop()
+        th.cuda.synchronize()
+        dev_loss = float((loss_d - th.stack(eager_losses)).abs().max() / th.stack(eager_losses).abs().max())
+        for _ in range(max(1, a.warmup // 10)):
+            fused_loop()
+            eager_loop()
+        th.cuda.synchronize()
+        t = {"fused": [], "eager": []}
+        for _ in range(5):
+            for name, fn, reps in (("fused", fused_loop, loops), ("eager", eager_loop, max(1, loops // 10))):
+                th.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    fn()
+                th.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) * 1e3 / (reps * n_upd))
+        lib.lib.morl_pcn_destroy(h)
+        fused, eager = float(np.median(t["fused"])), float(np.median(t["eager"]))
+        heads[head] = {"shape": dict(state_dim=D, reward_dim=R, action_dim=A, batch=B, hidden=H, updates_per_loop=n_upd),
+                       "fused_ms_per_update": fused, "fused_windows_ms": t["fused"], "eager_torch_ms_per_update": eager,
+                       "eager_windows_ms": t["eager"], "eager_over_fused": eager / fused,
+                       "first_loop_loss_rel_diff": dev_loss, "loops_per_window": {"fused": loops, "eager": max(1, loops // 10)}}
+    d = heads["discrete"]
+    out = {"metric": "PCN optimiser updates/sec (one-entry 50-update loop, discrete head)", "value": 1e3 / d["fused_ms_per_update"],
+           "unit": "updates/s", "n_gpus": 1, "steps": loops, "warmup": a.warmup, "ms_per_step": d["fused_ms_per_update"],
+           "higher_is_better": True, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "PCN.train() inner loop: 50 x update() at batch 256, hidden 64 (pcn.py:399, 458-459), one "
+                                  "morl_pcn_update_n call per loop; comparison: the same updates as eager torch ops on the same GPU"},
+           "heads": heads,
+           "roofline": {"bound": "latency", "kernel": "pcn_step_kernel", "achieved": None, "peak": None, "unit": None, "frac": None,
+                        "traffic": None, "note": "~10 MFLOP and < 1 MB per update: launch- and dependency-latency-bound"}}
+    print(json.dumps(out), file=RESULT_OUT, flush=True)
+
+
 def _claim_stdout():
     """stdout must carry exactly ONE line, rank 0's JSON: C libraries (RCCL prints a version banner to stdout, flushed
     at exit, i.e. after the JSON) and the other ranks are moved to stderr; the result is written to the saved descriptor."""
@@ -456,6 +548,8 @@ def main():
         return bench_gpi(a)
     if a.workload == "ens":
         return bench_ens(a)
+    if a.workload == "pcn":
+        return bench_pcn(a)
     from morl_baselines_amd.ac_engine import ALGO_CAPQL, ALGO_MOSAC, ALGO_TD3, ACEngine
 
     wl, shp = a.workload, SHAPES[a.workload]

@@ -806,6 +806,41 @@ int morl_ens_forward(morl_ens_ctx* ctx, const float* params, const float* logvar
 int morl_ens_mse(morl_ens_ctx* ctx, const float* params, const float* logvar_bounds, const float* mu, const float* sigma,
                  const float* x, const float* y, int rows, float* mse_out, void* stream);
 
+/* ================================================================================================
+ * Pareto Conditioned Networks (multi_policy/pcn/pcn.py)
+ *   model (pcn.py:63-103):  c = cat(desired_return, desired_horizon) * scaling_factor
+ *                           out = fc(sigmoid(s_emb(obs)) * sigmoid(c_emb(c))), fc = Linear-ReLU-Linear [-LogSoftmax]
+ *   update() (:202-236):    gather a batch, forward, cross entropy (discrete) / MSE (continuous), backward, Adam
+ *   _act (:302-322):        the no-grad forward
+ * Parameters are one flat fp32 vector in the order of model.parameters() without the frozen scaling_factor:
+ *   s_emb.0.weight [H][D], s_emb.0.bias [H], c_emb.0.weight [H][R+1], c_emb.0.bias [H], fc.0.weight [H][H], fc.0.bias [H],
+ *   fc.2.weight [A][H], fc.2.bias [A].
+ * Limits: state_dim 1..128, reward_dim 1..8, action_dim 1..32, hidden_dim 32 | 64 | 96 | 128, any batch >= 1 up to max_batch.
+ * The entries take scalars and pointers only; every pointer is device memory unless stated; nothing synchronises the host.
+ * ================================================================================================ */
+typedef struct morl_pcn_ctx morl_pcn_ctx;
+
+/* -1 (and morl_last_error) for a shape outside the limits */
+int64_t morl_pcn_param_count(int state_dim, int reward_dim, int action_dim, int hidden_dim);
+/* continuous: 0 = log-softmax head + cross entropy, 1 = linear head + MSE.  max_batch: largest B of morl_pcn_update_n. */
+int morl_pcn_create(morl_pcn_ctx** out, int state_dim, int reward_dim, int action_dim, int hidden_dim, int continuous,
+                    int max_batch);
+int morl_pcn_destroy(morl_pcn_ctx* ctx);
+/* Replace the transition table with n_rows rows of  obs [D] | action | return-to-go [R] | steps left [1]  (fp32; the action is its
+ * index as a float for the discrete head, action_dim floats for the continuous one).  rows: host or device memory; the context
+ * keeps a device copy of its own, ordered on `stream` after the updates already enqueued there. */
+int morl_pcn_set_table(morl_pcn_ctx* ctx, const float* rows, int64_t n_rows, void* stream);
+/* n optimiser steps, one launch each, enqueued back to back.  idx [n][B] int32 rows of the table (step k trains on idx[k]);
+ * scaling [R+1]; Adam with torch's defaults (betas 0.9 / 0.999, eps 1e-8), adam_steps_done = steps taken before this call.
+ * loss_out [n]; entropy_out [n] or NULL: sum over the batch of -sum_a p log p (discrete head; pcn.py:463);
+ * pred_out [B][A] or NULL: the predictions of the LAST step (what update() returns).  Results are bit-identical run to run. */
+int morl_pcn_update_n(morl_pcn_ctx* ctx, float* params, float* exp_avg, float* exp_avg_sq, const float* scaling, int n,
+                      const int32_t* idx, int B, double lr, int adam_steps_done, float* loss_out, float* entropy_out,
+                      float* pred_out, void* stream);
+/* out [rows][A] = model(obs [rows][D], desired_return [rows][R], desired_horizon [rows]): log-probabilities or actions. */
+int morl_pcn_forward(morl_pcn_ctx* ctx, const float* params, const float* scaling, const float* obs,
+                     const float* desired_return, const float* desired_horizon, int rows, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,3 +8,11 @@ __version__ = "0.1.0"
 
 from . import native, ops  # noqa: F401
 from .native import load_library  # noqa: F401
+
+
+def __getattr__(name):
+    # the agents import torch.nn modules and, where present, the reference's base classes: loaded on first use
+    if name == "PCN":
+        from .pcn import PCN
+        return PCN
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

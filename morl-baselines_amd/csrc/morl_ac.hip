@@ -2149,3 +2149,144 @@ extern "C" int morl_gpi_update_n_per(morl_gpi_ctx* c, float* q, const float* q_t
     }
     return MORL_OK;
 }
+
+
+// =====================================================================================================================
+// Pareto Conditioned Networks (include/morl_hip.h, "Pareto Conditioned Networks")
+// =====================================================================================================================
+#include "pcn_kernels.h"
+
+static_assert(PCN_MAX_R == MORL_MAX_OBJ, "PCN reward_dim limit is MORL_MAX_OBJ");
+static_assert(PCN_MAX_R + 1 <= PCN_CLD, "command row stride");
+
+struct morl_pcn_ctx {
+    PcnNet n{};
+    int max_batch = 0, max_tiles = 0;
+    int act_w = 0, row_w = 0;
+    float* table = nullptr;        // [table_cap floats]
+    int64_t table_cap = 0, table_rows = 0;
+    float* part = nullptr;         // [max_tiles][P]
+    float* lpart = nullptr;        // [max_tiles][2]
+    unsigned int* ticket = nullptr;
+};
+
+static int pcn_fill(PcnNet& n, int D, int R, int A, int H, int continuous) {
+    if (D < 1 || D > PCN_MAX_D) return fail(MORL_ERR_ARG, "PCN: state_dim %d outside 1..%d", D, PCN_MAX_D);
+    if (R < 1 || R > PCN_MAX_R) return fail(MORL_ERR_ARG, "PCN: reward_dim %d outside 1..%d", R, PCN_MAX_R);
+    if (A < 1 || A > PCN_MAX_A) return fail(MORL_ERR_ARG, "PCN: action_dim %d outside 1..%d", A, PCN_MAX_A);
+    if (H < 32 || H > PCN_MAX_H || H % 32 != 0)
+        return fail(MORL_ERR_ARG, "PCN: hidden_dim %d is not one of 32, 64, 96, 128", H);
+    n.D = D; n.R = R; n.A = A; n.H = H; n.C = R + 1; n.continuous = continuous ? 1 : 0;
+    int o = 0;
+    n.oWs = o; o += H * D;
+    n.obs = o; o += H;
+    n.oWc = o; o += H * n.C;
+    n.obc = o; o += H;
+    n.oW1 = o; o += H * H;
+    n.ob1 = o; o += H;
+    n.oW2 = o; o += A * H;
+    n.ob2 = o; o += A;
+    n.P = o;
+    return MORL_OK;
+}
+
+extern "C" int64_t morl_pcn_param_count(int state_dim, int reward_dim, int action_dim, int hidden_dim) {
+    PcnNet n{};
+    return pcn_fill(n, state_dim, reward_dim, action_dim, hidden_dim, 0) ? -1 : n.P;
+}
+
+extern "C" int morl_pcn_destroy(morl_pcn_ctx* c) {
+    if (!c) return MORL_OK;
+    for (void* p : {(void*)c->table, (void*)c->part, (void*)c->lpart, (void*)c->ticket})
+        if (p) (void)hipFree(p);
+    delete c;
+    return MORL_OK;
+}
+
+extern "C" int morl_pcn_create(morl_pcn_ctx** out, int state_dim, int reward_dim, int action_dim, int hidden_dim, int continuous,
+                               int max_batch) {
+    if (!out) return fail(MORL_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    PcnNet n{};
+    int rc = pcn_fill(n, state_dim, reward_dim, action_dim, hidden_dim, continuous);
+    if (rc) return rc;
+    if (max_batch < 1 || max_batch > (1 << 20)) return fail(MORL_ERR_ARG, "PCN: max_batch %d outside 1..%d", max_batch, 1 << 20);
+    morl_pcn_ctx* c = new (std::nothrow) morl_pcn_ctx();
+    if (!c) return fail(MORL_ERR_ALLOC, "out of host memory");
+    c->n = n;
+    c->max_batch = max_batch;
+    c->max_tiles = (max_batch + PCN_TB - 1) / PCN_TB;
+    c->act_w = continuous ? action_dim : 1;
+    c->row_w = state_dim + c->act_w + reward_dim + 1;
+    if ((rc = dmalloc((void**)&c->part, (size_t)c->max_tiles * n.P * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->lpart, (size_t)c->max_tiles * 2 * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->ticket, sizeof(unsigned int)))) {
+        morl_pcn_destroy(c);
+        return rc;
+    }
+    if (hipMemset(c->ticket, 0, sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        morl_pcn_destroy(c);
+        return fail(MORL_ERR_HIP, "PCN: workspace init failed");
+    }
+    *out = c;
+    return MORL_OK;
+}
+
+extern "C" int morl_pcn_set_table(morl_pcn_ctx* c, const float* rows, int64_t n_rows, void* stream) {
+    if (!c || !rows) return fail(MORL_ERR_ARG, "NULL argument");
+    if (n_rows < 1 || n_rows > (int64_t)INT32_MAX) return fail(MORL_ERR_ARG, "PCN: table of %lld rows", (long long)n_rows);
+    const int64_t need = n_rows * c->row_w;
+    if (need > c->table_cap) {
+        // (hipFree waits for the work that may still read the old table)
+        if (c->table) { (void)hipFree(c->table); c->table = nullptr; c->table_cap = 0; c->table_rows = 0; }
+        const int64_t cap = std::max<int64_t>(need * 2, 4096);
+        int rc = dmalloc((void**)&c->table, (size_t)cap * sizeof(float));
+        if (rc) return rc;
+        c->table_cap = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(c->table, rows, (size_t)need * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    c->table_rows = n_rows;
+    return MORL_OK;
+}
+
+extern "C" int morl_pcn_update_n(morl_pcn_ctx* c, float* params, float* exp_avg, float* exp_avg_sq, const float* scaling, int n,
+                                 const int32_t* idx, int B, double lr, int adam_steps_done, float* loss_out, float* entropy_out,
+                                 float* pred_out, void* stream) {
+    if (!c || !params || !exp_avg || !exp_avg_sq || !scaling || !idx || !loss_out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (n < 1) return fail(MORL_ERR_ARG, "n = %d updates", n);
+    if (B < 1 || B > c->max_batch) return fail(MORL_ERR_STATE, "PCN: batch %d outside 1..max_batch %d", B, c->max_batch);
+    if (c->table_rows < 1) return fail(MORL_ERR_STATE, "PCN: no transition table (morl_pcn_set_table)");
+    if (adam_steps_done < 0) return fail(MORL_ERR_ARG, "adam_steps_done %d", adam_steps_done);
+    if (entropy_out && c->n.continuous) return fail(MORL_ERR_ARG, "PCN: entropy_out is for the discrete head");
+    PcnStepArgs a{};
+    a.n = c->n;
+    a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.scaling = scaling;
+    a.table = c->table; a.table_rows = (int)c->table_rows; a.row_w = c->row_w; a.act_w = c->act_w;
+    a.B = B; a.ntiles = (B + PCN_TB - 1) / PCN_TB;
+    a.part = c->part; a.lpart = c->lpart; a.ticket = c->ticket;
+    a.inv_count = (float)(1.0 / (c->n.continuous ? (double)B * c->n.A : (double)B));
+    const double b1 = 0.9, b2 = 0.999;
+    a.one_minus_b1 = (float)(1.0 - b1); a.b2 = (float)b2; a.one_minus_b2 = (float)(1.0 - b2); a.eps = 1e-8f;
+    for (int k = 0; k < n; ++k) {
+        const int step = adam_steps_done + k + 1;
+        a.neg_step_size = (float)(-(lr / (1.0 - std::pow(b1, step))));
+        a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, step));
+        a.idx = idx + (size_t)k * B;
+        a.loss_out = loss_out + k;
+        a.ent_out = entropy_out ? entropy_out + k : nullptr;
+        a.pred_out = (k == n - 1) ? pred_out : nullptr;
+        hipLaunchKernelGGL(pcn_step_kernel, dim3(a.ntiles), dim3(PCN_THREADS), 0, (hipStream_t)stream, a);
+        LAUNCH_CHECK("pcn_step");
+    }
+    return MORL_OK;
+}
+
+extern "C" int morl_pcn_forward(morl_pcn_ctx* c, const float* params, const float* scaling, const float* obs,
+                                const float* desired_return, const float* desired_horizon, int rows, float* out, void* stream) {
+    if (!c || !params || !scaling || !obs || !desired_return || !desired_horizon || !out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (rows < 1) return fail(MORL_ERR_ARG, "PCN: rows = %d", rows);
+    hipLaunchKernelGGL(pcn_forward_kernel, dim3((rows + PCN_TB - 1) / PCN_TB), dim3(PCN_THREADS), 0, (hipStream_t)stream, c->n,
+                       params, scaling, obs, desired_return, desired_horizon, rows, out);
+    LAUNCH_CHECK("pcn_forward");
+    return MORL_OK;
+}

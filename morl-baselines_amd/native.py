@@ -258,6 +258,12 @@ _SIGNATURES = {
                                          C.c_void_p, C.c_int, C.POINTER(ACCfg), C.c_void_p, C.c_void_p, C.c_void_p]),
     "morl_ac_q_forward": (C.c_int, [C.c_void_p, C.POINTER(ACState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_int, C.c_void_p, C.c_void_p]),
+    "morl_pcn_param_count": (C.c_int64, [C.c_int] * 4),
+    "morl_pcn_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 6),
+    "morl_pcn_destroy": (C.c_int, [C.c_void_p]),
+    "morl_pcn_set_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "morl_pcn_update_n": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 4),
+    "morl_pcn_forward": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

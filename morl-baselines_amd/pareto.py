@@ -49,6 +49,19 @@ def filter_pareto_dominated(candidates: Union[np.ndarray, List], remove_duplicat
                                                     device=device)]
 
 
+def get_non_dominated_inds(solutions: np.ndarray) -> np.ndarray:
+    """``pareto.py:128-137``: boolean mask of the non-dominated points; of equal points the first is kept.  PCN calls it on at
+    most 100 returns per training iteration (``pcn.py:257, 286``), so it stays the reference's numpy loop: the heap order and the
+    commands that follow from it are then bit-identical to the reference's by construction."""
+    solutions = np.asarray(solutions)
+    is_efficient = np.ones(solutions.shape[0], dtype=bool)
+    for i, c in enumerate(solutions):
+        if is_efficient[i]:
+            is_efficient[is_efficient] = np.any(solutions[is_efficient] > c, axis=1)
+            is_efficient[i] = 1
+    return is_efficient
+
+
 def filter_convex_dominated(candidates: Union[np.ndarray, List], lib: Optional[NativeLib] = None, device=None):
     """``pareto.py:76-93``: QuickHull (SciPy, host) then the device Pareto filter."""
     from scipy.spatial import ConvexHull

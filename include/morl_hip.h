@@ -841,6 +841,49 @@ int morl_pcn_update_n(morl_pcn_ctx* ctx, float* params, float* exp_avg, float* e
 int morl_pcn_forward(morl_pcn_ctx* ctx, const float* params, const float* scaling, const float* obs,
                      const float* desired_return, const float* desired_horizon, int rows, float* out, void* stream);
 
+/* ================================================================================================
+ * Multi-objective PPO (single_policy/ser/mo_ppo.py)
+ *   MOPPONet (:160-235):    critic obs -> hidden (Tanh) -> [R];  actor_mean obs -> hidden (Tanh) -> [A];  actor_logstd [1][A]
+ *   update() (:509-554):    per minibatch: gather, forward, clipped policy loss + (clipped) value loss - ent_coef * entropy,
+ *                           backward, clip_grad_norm_, Adam(eps = 1e-5) -- one launch per minibatch step
+ *   __compute_advantages (:439-476), get_action_and_value / get_value (:205-235)
+ * Parameters are one flat fp32 vector in the order of MOPPONet.parameters():
+ *   actor_logstd [A], critic.0.weight [H0][D], critic.0.bias, critic.2.*, (critic.4.*), actor_mean.0.*, actor_mean.2.*,
+ *   (actor_mean.4.*) -- the .4 entries exist with two hidden layers only.
+ * Limits: obs_dim 1..128, action_dim 1..32, reward_dim 1..8, one or two hidden layers of width 32 | 64 | 96 | 128 each.
+ * The entries take scalars and pointers only; every pointer is device memory; nothing synchronises the host.
+ * ================================================================================================ */
+typedef struct morl_ppo_ctx morl_ppo_ctx;
+
+/* -1 (and morl_last_error) for a shape outside the limits; hidden1 is ignored when n_hidden == 1 */
+int64_t morl_ppo_param_count(int obs_dim, int action_dim, int reward_dim, int n_hidden, int hidden0, int hidden1);
+/* max_minibatch: largest M of morl_ppo_update_n */
+int morl_ppo_create(morl_ppo_ctx** out, int obs_dim, int action_dim, int reward_dim, int n_hidden, int hidden0, int hidden1,
+                    int max_minibatch);
+int morl_ppo_destroy(morl_ppo_ctx* ctx);
+/* Replace the context's rollout with T steps of E envs, row t * E + e:  obs [T*E][D], actions [T*E][A], logprobs [T*E],
+ * rewards [T*E][R], dones [T*E] (0 / 1 as floats: the done flag seen BEFORE step t, as PPOReplayBuffer stores it), values [T*E][R].
+ * The context keeps its own table, one row per (step, env):
+ *   obs | action | old log-prob | scalarised advantage | returns [R] | old values [R];  morl_ppo_gae fills the middle columns. */
+int morl_ppo_set_rollout(morl_ppo_ctx* ctx, const float* obs, const float* actions, const float* logprobs, const float* rewards,
+                         const float* dones, const float* values, int T, int E, void* stream);
+/* The reverse scan over the rollout: next_value [E][R], next_done [E], weights [R]; use_gae 0: discounted returns minus values.
+ * gamma * gae_lambda is formed in double.  returns_out [T*E][R] / advantages_out [T*E] (scalarised): copies, or NULL. */
+int morl_ppo_gae(morl_ppo_ctx* ctx, const float* next_value, const float* next_done, const float* weights, double gamma,
+                 double gae_lambda, int use_gae, float* returns_out, float* advantages_out, void* stream);
+/* n minibatch steps, one launch each, enqueued back to back.  idx [n][M] int32 rows of the rollout (step k trains on idx[k]);
+ * Adam with betas 0.9 / 0.999 and eps 1e-5, adam_steps_done = steps taken before this call.  norm_adv needs M >= 2.
+ * stats_out [n][8]: loss, pg_loss, v_loss, entropy, old_approx_kl, approx_kl, clipfrac, grad_norm (before clipping) of each step.
+ * Results are bit-identical run to run, and n steps in one call equal n calls of one step. */
+int morl_ppo_update_n(morl_ppo_ctx* ctx, float* params, float* exp_avg, float* exp_avg_sq, int n, const int32_t* idx, int M,
+                      double lr, int adam_steps_done, double clip_coef, double ent_coef, double vf_coef, double max_grad_norm,
+                      int clip_vloss, int norm_adv, float* stats_out, void* stream);
+/* No-grad get_action_and_value on obs [rows][D] with the standard-normal noise eps [rows][A]:
+ * action_out [rows][A] = mean + exp(logstd) * eps, logprob_out [rows] (summed over A), value_out [rows][R].
+ * value_only != 0 is get_value: the actor is skipped and eps / action_out / logprob_out may be NULL. */
+int morl_ppo_forward(morl_ppo_ctx* ctx, const float* params, const float* obs, const float* eps, int rows, int value_only,
+                     float* action_out, float* logprob_out, float* value_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "PCN":
         from .pcn import PCN
         return PCN
+    if name in ("MOPPO", "MOPPONet"):
+        from . import mo_ppo
+        return getattr(mo_ppo, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

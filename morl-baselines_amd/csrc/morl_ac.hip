@@ -2290,3 +2290,187 @@ extern "C" int morl_pcn_forward(morl_pcn_ctx* c, const float* params, const floa
     LAUNCH_CHECK("pcn_forward");
     return MORL_OK;
 }
+
+
+// =====================================================================================================================
+// Multi-objective PPO (include/morl_hip.h, "Multi-objective PPO")
+// =====================================================================================================================
+#include "ppo_kernels.h"
+
+static_assert(PPO_MAX_R == MORL_MAX_OBJ, "MO-PPO reward_dim limit is MORL_MAX_OBJ");
+
+struct morl_ppo_ctx {
+    PpoNet n{};
+    int max_minibatch = 0, max_tiles = 0, row_w = 0;
+    float* table = nullptr;        // [rows_cap][row_w]
+    float* rewards = nullptr;      // [rows_cap][R]
+    float* dones = nullptr;        // [rows_cap]
+    int64_t rows_cap = 0;
+    int T = 0, E = 0, have_gae = 0;
+    float* part = nullptr;         // [max_tiles][P]
+    float* lpart = nullptr;        // [max_tiles][PPO_NPART]
+    unsigned int* ticket = nullptr;
+};
+
+static int ppo_fill(PpoNet& n, int D, int A, int R, int nh, int h0, int h1) {
+    if (D < 1 || D > PPO_MAX_D) return fail(MORL_ERR_ARG, "MO-PPO: obs_dim %d outside 1..%d", D, PPO_MAX_D);
+    if (A < 1 || A > PPO_MAX_A) return fail(MORL_ERR_ARG, "MO-PPO: action_dim %d outside 1..%d", A, PPO_MAX_A);
+    if (R < 1 || R > PPO_MAX_R) return fail(MORL_ERR_ARG, "MO-PPO: reward_dim %d outside 1..%d", R, PPO_MAX_R);
+    if (nh < 1 || nh > 2) return fail(MORL_ERR_ARG, "MO-PPO: n_hidden %d is not 1 or 2 hidden layers", nh);
+    const int hs[2] = {h0, h1};
+    for (int l = 0; l < nh; ++l)
+        if (hs[l] < 32 || hs[l] > PPO_MAX_H || hs[l] % 32 != 0)
+            return fail(MORL_ERR_ARG, "MO-PPO: hidden width %d (layer %d) is not one of 32, 64, 96, 128", hs[l], l);
+    n.D = D; n.A = A; n.R = R; n.nh = nh; n.H1 = h0; n.H2 = (nh == 2) ? h1 : h0;
+    int o = 0, t = 0;
+    auto take = [&](int count) { const int at = o; n.tstart[t++] = o; o += count; return at; };
+    n.oLs = take(A);
+    for (int which = 0; which < 2; ++which) {
+        PpoMlp& m = which ? n.a : n.c;
+        const int N = which ? A : R;
+        m.oW0 = take(n.H1 * D);
+        m.ob0 = take(n.H1);
+        m.oW1 = m.ob1 = 0;
+        if (nh == 2) {
+            m.oW1 = take(n.H2 * n.H1);
+            m.ob1 = take(n.H2);
+        }
+        m.oWo = take(N * n.H2);
+        m.obo = take(N);
+    }
+    n.P = o;
+    n.ntensors = t;
+    for (int i = t; i <= PPO_MAX_TENSORS; ++i) n.tstart[i] = o;
+    return MORL_OK;
+}
+
+extern "C" int64_t morl_ppo_param_count(int obs_dim, int action_dim, int reward_dim, int n_hidden, int hidden0, int hidden1) {
+    PpoNet n{};
+    return ppo_fill(n, obs_dim, action_dim, reward_dim, n_hidden, hidden0, hidden1) ? -1 : n.P;
+}
+
+extern "C" int morl_ppo_destroy(morl_ppo_ctx* c) {
+    if (!c) return MORL_OK;
+    for (void* p : {(void*)c->table, (void*)c->rewards, (void*)c->dones, (void*)c->part, (void*)c->lpart, (void*)c->ticket})
+        if (p) (void)hipFree(p);
+    delete c;
+    return MORL_OK;
+}
+
+extern "C" int morl_ppo_create(morl_ppo_ctx** out, int obs_dim, int action_dim, int reward_dim, int n_hidden, int hidden0,
+                               int hidden1, int max_minibatch) {
+    if (!out) return fail(MORL_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    PpoNet n{};
+    int rc = ppo_fill(n, obs_dim, action_dim, reward_dim, n_hidden, hidden0, hidden1);
+    if (rc) return rc;
+    if (max_minibatch < 1 || max_minibatch > (1 << 20))
+        return fail(MORL_ERR_ARG, "MO-PPO: max_minibatch %d outside 1..%d", max_minibatch, 1 << 20);
+    morl_ppo_ctx* c = new (std::nothrow) morl_ppo_ctx();
+    if (!c) return fail(MORL_ERR_ALLOC, "out of host memory");
+    c->n = n;
+    c->max_minibatch = max_minibatch;
+    c->max_tiles = (max_minibatch + PPO_TB - 1) / PPO_TB;
+    c->row_w = obs_dim + action_dim + 2 + 2 * reward_dim;
+    if ((rc = dmalloc((void**)&c->part, (size_t)c->max_tiles * n.P * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->lpart, (size_t)c->max_tiles * PPO_NPART * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->ticket, sizeof(unsigned int)))) {
+        morl_ppo_destroy(c);
+        return rc;
+    }
+    if (hipMemset(c->ticket, 0, sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        morl_ppo_destroy(c);
+        return fail(MORL_ERR_HIP, "MO-PPO: workspace init failed");
+    }
+    *out = c;
+    return MORL_OK;
+}
+
+extern "C" int morl_ppo_set_rollout(morl_ppo_ctx* c, const float* obs, const float* actions, const float* logprobs,
+                                    const float* rewards, const float* dones, const float* values, int T, int E, void* stream) {
+    if (!c || !obs || !actions || !logprobs || !rewards || !dones || !values) return fail(MORL_ERR_ARG, "NULL argument");
+    if (T < 1 || E < 1 || (int64_t)T * E > (int64_t)(1 << 24))
+        return fail(MORL_ERR_ARG, "MO-PPO: rollout of %d steps x %d envs (at most %d rows)", T, E, 1 << 24);
+    const int64_t rows = (int64_t)T * E;
+    const int R = c->n.R;
+    if (rows > c->rows_cap) {
+        // (hipFree waits for the work that may still read the old buffers)
+        for (float** p : {&c->table, &c->rewards, &c->dones})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        c->rows_cap = 0; c->T = c->E = 0;
+        int rc;
+        if ((rc = dmalloc((void**)&c->table, (size_t)rows * c->row_w * sizeof(float))) ||
+            (rc = dmalloc((void**)&c->rewards, (size_t)rows * R * sizeof(float))) ||
+            (rc = dmalloc((void**)&c->dones, (size_t)rows * sizeof(float))))
+            return rc;
+        c->rows_cap = rows;
+    }
+    HIP_TRY(hipMemcpyAsync(c->rewards, rewards, (size_t)rows * R * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(c->dones, dones, (size_t)rows * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    const int64_t total = rows * c->row_w;
+    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 1024);
+    hipLaunchKernelGGL(ppo_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c->n.D, c->n.A, R, c->row_w, (int)rows, obs,
+                       actions, logprobs, values, c->table);
+    LAUNCH_CHECK("ppo_pack");
+    c->T = T; c->E = E; c->have_gae = 0;
+    return MORL_OK;
+}
+
+extern "C" int morl_ppo_gae(morl_ppo_ctx* c, const float* next_value, const float* next_done, const float* weights, double gamma,
+                            double gae_lambda, int use_gae, float* returns_out, float* advantages_out, void* stream) {
+    if (!c || !next_value || !next_done || !weights) return fail(MORL_ERR_ARG, "NULL argument");
+    if (c->T < 1) return fail(MORL_ERR_STATE, "MO-PPO: no rollout (morl_ppo_set_rollout)");
+    hipLaunchKernelGGL(ppo_gae_kernel, dim3((c->E + 63) / 64), dim3(64), 0, (hipStream_t)stream, c->T, c->E, c->n.R, c->row_w,
+                       c->n.D + c->n.A + 1, c->table, c->rewards, c->dones, next_value, next_done, weights, (float)gamma,
+                       (float)(gamma * gae_lambda), use_gae ? 1 : 0, returns_out, advantages_out);
+    LAUNCH_CHECK("ppo_gae");
+    c->have_gae = 1;
+    return MORL_OK;
+}
+
+extern "C" int morl_ppo_update_n(morl_ppo_ctx* c, float* params, float* exp_avg, float* exp_avg_sq, int n, const int32_t* idx, int M,
+                                 double lr, int adam_steps_done, double clip_coef, double ent_coef, double vf_coef,
+                                 double max_grad_norm, int clip_vloss, int norm_adv, float* stats_out, void* stream) {
+    if (!c || !params || !exp_avg || !exp_avg_sq || !idx || !stats_out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (n < 1) return fail(MORL_ERR_ARG, "n = %d updates", n);
+    if (M < 1 || M > c->max_minibatch)
+        return fail(MORL_ERR_STATE, "MO-PPO: minibatch %d outside 1..max_minibatch %d", M, c->max_minibatch);
+    if (norm_adv && M < 2) return fail(MORL_ERR_ARG, "MO-PPO: norm_adv needs a minibatch of at least 2 rows (std of %d)", M);
+    if (c->T < 1) return fail(MORL_ERR_STATE, "MO-PPO: no rollout (morl_ppo_set_rollout)");
+    if (!c->have_gae) return fail(MORL_ERR_STATE, "MO-PPO: the rollout has no advantages yet (morl_ppo_gae)");
+    if (adam_steps_done < 0) return fail(MORL_ERR_ARG, "adam_steps_done %d", adam_steps_done);
+    PpoStepArgs a{};
+    a.n = c->n;
+    a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
+    a.table = c->table; a.table_rows = c->T * c->E; a.row_w = c->row_w;
+    a.M = M; a.ntiles = (M + PPO_TB - 1) / PPO_TB;
+    a.part = c->part; a.lpart = c->lpart; a.ticket = c->ticket;
+    a.clip_lo = (float)(1.0 - clip_coef); a.clip_hi = (float)(1.0 + clip_coef); a.clip_coef = (float)clip_coef;
+    a.ent_coef = (float)ent_coef; a.vf_coef = (float)vf_coef; a.max_grad_norm = (float)max_grad_norm;
+    a.clip_vloss = clip_vloss ? 1 : 0; a.norm_adv = norm_adv ? 1 : 0;
+    a.inv_M = (float)(1.0 / M); a.inv_MR = (float)(1.0 / ((double)M * c->n.R)); a.inv_Mm1 = M > 1 ? (float)(1.0 / (M - 1)) : 0.0f;
+    a.fM = (float)M; a.fMR = (float)((double)M * c->n.R);
+    const double b1 = 0.9, b2 = 0.999;
+    a.one_minus_b1 = (float)(1.0 - b1); a.b2 = (float)b2; a.one_minus_b2 = (float)(1.0 - b2); a.eps = 1e-5f;
+    for (int k = 0; k < n; ++k) {
+        const int step = adam_steps_done + k + 1;
+        a.neg_step_size = (float)(-(lr / (1.0 - std::pow(b1, step))));
+        a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, step));
+        a.idx = idx + (size_t)k * M;
+        a.stats_out = stats_out + (size_t)k * PPO_NSTATS;
+        hipLaunchKernelGGL(ppo_step_kernel, dim3(a.ntiles), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
+        LAUNCH_CHECK("ppo_step");
+    }
+    return MORL_OK;
+}
+
+extern "C" int morl_ppo_forward(morl_ppo_ctx* c, const float* params, const float* obs, const float* eps, int rows, int value_only,
+                                float* action_out, float* logprob_out, float* value_out, void* stream) {
+    if (!c || !params || !obs || !value_out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (!value_only && (!eps || !action_out || !logprob_out)) return fail(MORL_ERR_ARG, "MO-PPO: eps / action_out / logprob_out is NULL");
+    if (rows < 1) return fail(MORL_ERR_ARG, "MO-PPO: rows = %d", rows);
+    hipLaunchKernelGGL(ppo_forward_kernel, dim3((rows + PPO_TB - 1) / PPO_TB), dim3(PPO_THREADS), 0, (hipStream_t)stream, c->n, params,
+                       obs, eps, rows, value_only ? 1 : 0, action_out, logprob_out, value_out);
+    LAUNCH_CHECK("ppo_forward");
+    return MORL_OK;
+}

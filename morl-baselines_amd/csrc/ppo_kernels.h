@@ -1,0 +1,523 @@
+// Multi-objective PPO (single_policy/ser/mo_ppo.py): one minibatch step of MOPPO.update() (mo_ppo.py:509-554) as ONE launch, the
+// reverse scan of __compute_advantages (mo_ppo.py:439-476) and the no-grad get_action_and_value (mo_ppo.py:215-235).  fp32.
+//
+//   critic:      obs -> hidden (Tanh) -> [R]          actor_mean: obs -> hidden (Tanh) -> [A]          actor_logstd [1][A]
+//   newlogprob = sum_a Normal(mean, exp(logstd)).log_prob(action),  ratio = exp(newlogprob - old log-prob)
+//   pg   = mean_b max(-adv ratio, -adv clamp(ratio, 1 - c, 1 + c))                       (adv normalised over the minibatch)
+//   v    = 0.5 mean_{b,k} max((v - ret)^2, (old + clamp(v - old, -c, c) - ret)^2)        (or the unclipped square alone)
+//   loss = pg - ent_coef * entropy + vf_coef * v;  clip_grad_norm_(max_grad_norm);  Adam(eps = 1e-5)
+//
+// Structure: that of pcn_kernels.h.  A workgroup owns PPO_TB = 16 rows of the minibatch: it gathers them from the rollout table,
+// runs the critic forward and backward, then the actor forward and backward through the same LDS buffers, and writes its share of
+// the gradient -- a full-length partial -- to part[tile][P].  The workgroup that draws the last ticket sums the partials in tile
+// order, forms the clip scale, applies Adam, writes the step's statistics and re-arms the ticket.  No grid barrier, no
+// floating-point atomics, nobody waits.  Unlike pcn_kernels.h the transposed products of the backward pass read their weights
+// from an LDS stage (ppo_dense_t), not one L2 load per FMA, and the last workgroup loads four partials before it adds them.
+#pragma once
+#include "pcn_kernels.h"
+
+namespace morl {
+
+constexpr int PPO_THREADS = PCN_THREADS;
+constexpr int PPO_TB = PCN_TB;          // minibatch rows per workgroup
+constexpr int PPO_MAX_H = 128;          // a hidden width (a multiple of 32)
+constexpr int PPO_MAX_D = 128;          // obs_dim
+constexpr int PPO_MAX_A = 32;           // action_dim
+constexpr int PPO_MAX_R = 8;            // reward_dim (MORL_MAX_OBJ)
+constexpr int PPO_MAX_TENSORS = 13;     // actor_logstd + 2 networks x 3 layers x (weight, bias)
+constexpr int PPO_NSTATS = 8;           // loss, pg_loss, v_loss, entropy, old_approx_kl, approx_kl, clipfrac, grad_norm
+constexpr int PPO_NPART = 5;            // per-tile sums: pg, v, -logratio, (ratio - 1) - logratio, clipped rows
+constexpr float PPO_HALF_LOG_2PI = 0.91893853320467274178f;   // log(sqrt(2 pi))
+static_assert(PPO_MAX_H <= PCN_MAX_H && PPO_THREADS == 256 && PPO_TB == 16, "pcn_dense / pcn_dw are shared");
+
+// one of the two MLPs as a map into the flat parameter vector; with one hidden layer W1 / b1 are absent (H2 == H1, nh == 1)
+struct PpoMlp {
+    int oW0, ob0, oW1, ob1, oWo, obo;
+};
+// the flat vector in the order of MOPPONet.parameters(): actor_logstd, critic.*, actor_mean.*
+struct PpoNet {
+    int D, A, R, nh, H1, H2;   // H2: width of the last hidden layer
+    int oLs;
+    PpoMlp c, a;
+    int P, ntensors;
+    int tstart[PPO_MAX_TENSORS + 1];   // tensor boundaries (clip_grad_norm_ takes the 2-norm of the per-tensor 2-norms)
+};
+
+struct PpoLds {
+    float w[PCN_MAX_H * PCN_WLD];     // staged weight chunk; the last workgroup's per-tensor sums of squares
+    float x[PPO_TB * PPO_MAX_D];      // observations
+    float h1[PPO_TB * PPO_MAX_H];     // tanh(layer 0)
+    float h2[PPO_TB * PPO_MAX_H];     // tanh(layer 1); backward: d/d(its pre-activation)
+    float d[PPO_TB * PPO_MAX_H];      // backward: d/d(a hidden activation), then d/d(layer 0 pre-activation)
+    float out[PPO_TB * PPO_MAX_A];    // value [R] or action mean [A] of a row
+    float dout[PPO_TB * PPO_MAX_A];   // d loss / d out
+    float act[PPO_TB * PPO_MAX_A];    // the stored action; forward kernel: the noise
+    float row[PPO_TB * 4];            // per row: old log-prob, advantage, d loss / d newlogprob
+    float ret[PPO_TB * PPO_MAX_R], oldv[PPO_TB * PPO_MAX_R];
+    float red[PPO_THREADS];
+    float rs[PPO_TB * PPO_NPART];     // per-row loss terms
+    float stat[4];                    // advantage mean, 1 / (std + 1e-8), clip scale, total norm
+    int last;
+};
+static_assert(sizeof(PpoLds) <= 64 * 1024, "PPO tile state must fit 64 KB of static LDS");
+static_assert(PPO_MAX_TENSORS * PPO_THREADS <= PCN_MAX_H * PCN_WLD, "per-tensor sums of squares reuse the weight stage");
+static_assert(32 * (PPO_MAX_H + 1) <= PCN_MAX_H * PCN_WLD, "transposed stage: 32 rows of a weight");
+
+// forward of one MLP on the tile's rows in L.x: tanh activations in L.h1 (/ L.h2), the head's output in L.out [16][N]
+__device__ __forceinline__ void ppo_mlp_forward(PpoLds& L, const PpoNet& n, const PpoMlp& m, const float* __restrict__ p, int N) {
+    const int tid = (int)threadIdx.x;
+    pcn_dense(L.w, p + m.oW0, p + m.ob0, n.H1, n.D, L.x, n.D, L.h1, n.H1);
+    for (int o = tid; o < PPO_TB * n.H1; o += PPO_THREADS) L.h1[o] = tanhf(L.h1[o]);
+    const float* hl = L.h1;
+    if (n.nh == 2) {
+        pcn_dense(L.w, p + m.oW1, p + m.ob1, n.H2, n.H1, L.h1, n.H1, L.h2, n.H2);
+        for (int o = tid; o < PPO_TB * n.H2; o += PPO_THREADS) L.h2[o] = tanhf(L.h2[o]);
+        hl = L.h2;
+    }
+    pcn_dense(L.w, p + m.oWo, p + m.obo, N, n.H2, hl, n.H2, L.out, N);
+}
+
+// z[r][k] = sum_j dz[r][j] W[j][k] for the 16 rows (W [N][K] row-major, global): W goes through LDS 32 rows at a time, a
+// work-item owns column k of four rows, products are accumulated in j order.  Ends with a barrier.
+__device__ __forceinline__ void ppo_dense_t(float* sw, const float* __restrict__ W, int N, int K, const float* dz, int ldz, float* z) {
+    const int tid = (int)threadIdx.x, ld = K + 1;
+    for (int j0 = 0; j0 < N; j0 += 32) {
+        const int jc = min(32, N - j0);
+        __syncthreads();
+        for (int o = tid; o < jc * K; o += PPO_THREADS) {
+            const int jj = o / K, k = o - jj * K;
+            sw[jj * ld + k] = W[(size_t)(j0 + jj) * K + k];
+        }
+        __syncthreads();
+        for (int o = tid; o < 4 * K; o += PPO_THREADS) {
+            const int rg = o / K, k = o - rg * K;
+            float acc[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[u] = (j0 == 0) ? 0.0f : z[(rg * 4 + u) * K + k];
+            for (int jj = 0; jj < jc; ++jj) {
+                const float w = sw[jj * ld + k];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) acc[u] = fmaf(dz[(rg * 4 + u) * ldz + j0 + jj], w, acc[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) z[(rg * 4 + u) * K + k] = acc[u];
+        }
+    }
+    __syncthreads();
+}
+
+// backward of one MLP from L.dout [16][N]: writes the tile's weight-gradient partial (row order) into part
+__device__ __forceinline__ void ppo_mlp_backward(PpoLds& L, const PpoNet& n, const PpoMlp& m, const float* __restrict__ p,
+                                                 float* __restrict__ part, int N) {
+    const int tid = (int)threadIdx.x;
+    float* hl = (n.nh == 2) ? L.h2 : L.h1;
+    pcn_dw(part + m.oWo, L.dout, N, hl, n.H2, N, n.H2);
+    pcn_db(part + m.obo, L.dout, N, N);
+    ppo_dense_t(L.w, p + m.oWo, N, n.H2, L.dout, N, L.d);
+    if (n.nh == 2) {
+        for (int o = tid; o < PPO_TB * n.H2; o += PPO_THREADS) {
+            const float t = L.h2[o];
+            L.h2[o] = __fmul_rn(L.d[o], __fsub_rn(1.0f, __fmul_rn(t, t)));
+        }
+        __syncthreads();
+        pcn_dw(part + m.oW1, L.h2, n.H2, L.h1, n.H1, n.H2, n.H1);
+        pcn_db(part + m.ob1, L.h2, n.H2, n.H2);
+        ppo_dense_t(L.w, p + m.oW1, n.H2, n.H1, L.h2, n.H2, L.d);
+    }
+    for (int o = tid; o < PPO_TB * n.H1; o += PPO_THREADS) {
+        const float t = L.h1[o];
+        L.d[o] = __fmul_rn(L.d[o], __fsub_rn(1.0f, __fmul_rn(t, t)));
+    }
+    __syncthreads();
+    pcn_dw(part + m.oW0, L.d, n.H1, L.x, n.D, n.H1, n.D);
+    pcn_db(part + m.ob0, L.d, n.H1, n.H1);
+    __syncthreads();
+}
+
+// sum of red[0 .. 255] by a fixed tree: the same bits in every workgroup
+__device__ __forceinline__ float ppo_tree_sum(float* red, float v) {
+    const int tid = (int)threadIdx.x;
+    __syncthreads();
+    red[tid] = v;
+    __syncthreads();
+    for (int s = PPO_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = __fadd_rn(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// no-grad get_action_and_value / get_value
+// ---------------------------------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(PPO_THREADS) void ppo_forward_kernel(PpoNet n, const float* __restrict__ params,
+                                                                        const float* __restrict__ obs,
+                                                                        const float* __restrict__ eps, int rows, int value_only,
+                                                                        float* __restrict__ action_out,
+                                                                        float* __restrict__ logprob_out,
+                                                                        float* __restrict__ value_out) {
+    __shared__ PpoLds L;
+    const int tid = (int)threadIdx.x, row0 = (int)blockIdx.x * PPO_TB;
+    for (int o = tid; o < PPO_TB * n.D; o += PPO_THREADS) {
+        const int r = o / n.D, d = o - r * n.D;
+        L.x[o] = (row0 + r < rows) ? obs[(size_t)(row0 + r) * n.D + d] : 0.0f;
+    }
+    ppo_mlp_forward(L, n, n.c, params, n.R);
+    for (int o = tid; o < PPO_TB * n.R; o += PPO_THREADS) {
+        const int r = o / n.R;
+        if (row0 + r < rows) value_out[(size_t)row0 * n.R + o] = L.out[o];
+    }
+    if (value_only) return;
+    for (int o = tid; o < PPO_TB * n.A; o += PPO_THREADS) {
+        const int r = o / n.A;
+        L.act[o] = (row0 + r < rows) ? eps[(size_t)row0 * n.A + o] : 0.0f;
+    }
+    ppo_mlp_forward(L, n, n.a, params, n.A);
+    if (tid < PPO_TB && row0 + tid < rows) {
+        const int r = tid;
+        float lp = 0.0f;
+        for (int k = 0; k < n.A; ++k) {
+            const float sd = expf(params[n.oLs + k]), mean = L.out[r * n.A + k];
+            const float act = __fadd_rn(mean, __fmul_rn(sd, L.act[r * n.A + k]));        // Normal.sample(): loc + eps * scale
+            const float diff = __fsub_rn(act, mean);
+            const float var = __fmul_rn(sd, sd);
+            const float t = __fdiv_rn(-__fmul_rn(diff, diff), __fmul_rn(2.0f, var));
+            lp = __fadd_rn(lp, __fsub_rn(__fsub_rn(t, logf(sd)), PPO_HALF_LOG_2PI));
+            action_out[(size_t)(row0 + r) * n.A + k] = act;
+        }
+        logprob_out[row0 + r] = lp;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// rollout table: one row per (step, env):  obs [D] | action [A] | old log-prob | scalarised advantage | returns [R] | old values [R]
+// ---------------------------------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void ppo_pack_kernel(int D, int A, int R, int row_w, int rows,
+                                                              const float* __restrict__ obs, const float* __restrict__ actions,
+                                                              const float* __restrict__ logprobs, const float* __restrict__ values,
+                                                              float* __restrict__ table) {
+    const long long total = (long long)rows * row_w;
+    for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (long long)gridDim.x * blockDim.x) {
+        const int row = (int)(o / row_w), c = (int)(o - (long long)row * row_w);
+        float v = 0.0f;                                         // advantage and returns: written by ppo_gae_kernel
+        if (c < D) v = obs[(size_t)row * D + c];
+        else if (c < D + A) v = actions[(size_t)row * A + (c - D)];
+        else if (c == D + A) v = logprobs[row];
+        else if (c >= D + A + 2 + R) v = values[(size_t)row * R + (c - (D + A + 2 + R))];
+        table[o] = v;
+    }
+}
+
+// __compute_advantages: one work-item per env runs the reverse scan of all its objectives
+//   gae:  delta = r + gamma * next_v * nonterminal - v;  last = delta + (gamma * gae_lambda) * nonterminal * last;  returns = last + v
+//   else: returns = r + gamma * nonterminal * next_return;  advantage = returns - v
+// and scalarises: advantages @ weights, summed over the objectives in index order
+static __global__ __launch_bounds__(64) void ppo_gae_kernel(int T, int E, int R, int row_w, int adv_col, float* __restrict__ table,
+                                                            const float* __restrict__ rewards, const float* __restrict__ dones,
+                                                            const float* __restrict__ next_value, const float* __restrict__ next_done,
+                                                            const float* __restrict__ weights, float gamma, float gamma_lambda,
+                                                            int use_gae, float* __restrict__ returns_out, float* __restrict__ adv_out) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= E) return;
+    float carry[PPO_MAX_R], nextv[PPO_MAX_R];
+#pragma unroll
+    for (int k = 0; k < PPO_MAX_R; ++k) {
+        carry[k] = 0.0f;
+        nextv[k] = (k < R) ? next_value[e * R + k] : 0.0f;
+    }
+    float nonterminal = __fsub_rn(1.0f, next_done[e]);
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t row = (size_t)t * E + e;
+        float* trow = table + row * row_w + adv_col;          // advantage | returns [R] | values [R]
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < PPO_MAX_R; ++k) {
+            if (k < R) {
+                const float r = rewards[row * R + k], v = trow[1 + R + k];
+                float adv, ret;
+                if (use_gae) {
+                    const float delta = __fsub_rn(__fadd_rn(r, __fmul_rn(__fmul_rn(gamma, nextv[k]), nonterminal)), v);
+                    adv = __fadd_rn(delta, __fmul_rn(__fmul_rn(gamma_lambda, nonterminal), carry[k]));
+                    carry[k] = adv;
+                    ret = __fadd_rn(adv, v);
+                    nextv[k] = v;
+                } else {
+                    const float nr = (t == T - 1) ? nextv[k] : carry[k];
+                    ret = __fadd_rn(r, __fmul_rn(__fmul_rn(gamma, nonterminal), nr));
+                    carry[k] = ret;
+                    adv = __fsub_rn(ret, v);
+                }
+                trow[1 + k] = ret;
+                if (returns_out != nullptr) returns_out[row * R + k] = ret;
+                s = __fadd_rn(s, __fmul_rn(adv, weights[k]));
+            }
+        }
+        trow[0] = s;
+        if (adv_out != nullptr) adv_out[row] = s;
+        nonterminal = __fsub_rn(1.0f, dones[row]);            // what step t - 1 sees as its successor's done flag
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// one minibatch step
+// ---------------------------------------------------------------------------------------------------------------------
+struct PpoStepArgs {
+    PpoNet n;
+    float* params;                 // [P]  read by every tile, stepped by the last workgroup
+    float* exp_avg;                // [P]
+    float* exp_avg_sq;             // [P]
+    const float* table;            // [table_rows][row_w]
+    int table_rows, row_w;
+    const int* idx;                // [M] rows of the table, this step's minibatch
+    int M, ntiles;
+    float* part;                   // [ntiles][P] gradient partials
+    float* lpart;                  // [ntiles][PPO_NPART] loss partial sums
+    unsigned int* ticket;          // arrival counter, zero between launches
+    float* stats_out;              // [PPO_NSTATS]
+    float clip_lo, clip_hi, clip_coef, ent_coef, vf_coef, max_grad_norm;
+    int clip_vloss, norm_adv;
+    float inv_M, inv_MR, inv_Mm1, fM, fMR;    // fM = M, fMR = M * R: a mean is a sum DIVIDED by its count, as torch forms it
+    float one_minus_b1, b2, one_minus_b2, neg_step_size, bc2_sqrt, eps;
+};
+
+static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArgs a) {
+    __shared__ PpoLds L;
+    const PpoNet& n = a.n;
+    const int tid = (int)threadIdx.x, tile = (int)blockIdx.x, row0 = tile * PPO_TB;
+    const int valid = min(PPO_TB, a.M - row0);
+    const float* p = a.params;
+    const int ao = n.D, lo = n.D + n.A, adv_col = lo + 1, ro = lo + 2, vo = ro + n.R;
+
+    // ---- gather (mo_ppo.py:509-511): table row idx[b] -> observation, action, old log-prob, advantage, returns, old values
+    for (int o = tid; o < PPO_TB * n.D; o += PPO_THREADS) {
+        const int r = o / n.D, d = o - r * n.D;
+        float v = 0.0f;
+        if (r < valid) {
+            const int row = min(max(a.idx[row0 + r], 0), a.table_rows - 1);
+            v = a.table[(size_t)row * a.row_w + d];
+        }
+        L.x[o] = v;
+    }
+    for (int o = tid; o < PPO_TB * n.A; o += PPO_THREADS) {
+        const int r = o / n.A, k = o - r * n.A;
+        float v = 0.0f;
+        if (r < valid) {
+            const int row = min(max(a.idx[row0 + r], 0), a.table_rows - 1);
+            v = a.table[(size_t)row * a.row_w + ao + k];
+        }
+        L.act[o] = v;
+    }
+    for (int o = tid; o < PPO_TB * n.R; o += PPO_THREADS) {
+        const int r = o / n.R, k = o - r * n.R;
+        float ret = 0.0f, ov = 0.0f;
+        if (r < valid) {
+            const int row = min(max(a.idx[row0 + r], 0), a.table_rows - 1);
+            ret = a.table[(size_t)row * a.row_w + ro + k];
+            ov = a.table[(size_t)row * a.row_w + vo + k];
+        }
+        L.ret[o] = ret;
+        L.oldv[o] = ov;
+    }
+    if (tid < PPO_TB) {
+        float lp = 0.0f, adv = 0.0f;
+        if (tid < valid) {
+            const int row = min(max(a.idx[row0 + tid], 0), a.table_rows - 1);
+            lp = a.table[(size_t)row * a.row_w + lo];
+            adv = a.table[(size_t)row * a.row_w + adv_col];
+        }
+        L.row[tid * 4] = lp;
+        L.row[tid * 4 + 1] = adv;
+    }
+
+    // ---- advantage normalisation (mo_ppo.py:527-528): mean and unbiased std of all M advantages, read in minibatch order and
+    // reduced by the same tree in every workgroup
+    if (a.norm_adv) {
+        float s = 0.0f;
+        for (int b = tid; b < a.M; b += PPO_THREADS) {
+            const int row = min(max(a.idx[b], 0), a.table_rows - 1);
+            s = __fadd_rn(s, a.table[(size_t)row * a.row_w + adv_col]);
+        }
+        const float mean = __fdiv_rn(ppo_tree_sum(L.red, s), a.fM);
+        float q = 0.0f;
+        for (int b = tid; b < a.M; b += PPO_THREADS) {
+            const int row = min(max(a.idx[b], 0), a.table_rows - 1);
+            const float dlt = __fsub_rn(a.table[(size_t)row * a.row_w + adv_col], mean);
+            q = fmaf(dlt, dlt, q);
+        }
+        const float var = __fmul_rn(ppo_tree_sum(L.red, q), a.inv_Mm1);
+        if (tid == 0) {
+            L.stat[0] = mean;
+            L.stat[1] = __fadd_rn(__fsqrt_rn(var), 1e-8f);
+        }
+    }
+    __syncthreads();
+
+    float* part = a.part + (size_t)tile * n.P;
+
+    // ---- critic: forward, value loss (mo_ppo.py:535-547) and its gradient, backward
+    ppo_mlp_forward(L, n, n.c, p, n.R);
+    if (tid < PPO_TB) {
+        const int r = tid;
+        float vsum = 0.0f;
+        const float gscale = __fmul_rn(__fmul_rn(0.5f, a.vf_coef), a.inv_MR);
+        for (int k = 0; k < n.R; ++k) {
+            const float v = L.out[r * n.R + k], ret = L.ret[r * n.R + k], ov = L.oldv[r * n.R + k];
+            float g = 0.0f;
+            if (r < valid) {
+                const float du = __fsub_rn(v, ret);
+                const float u = __fmul_rn(du, du);
+                g = __fmul_rn(2.0f, du);
+                float m = u;
+                if (a.clip_vloss) {
+                    const float dv = __fsub_rn(v, ov);
+                    const float vc = __fadd_rn(ov, fminf(fmaxf(dv, -a.clip_coef), a.clip_coef));
+                    const float dc = __fsub_rn(vc, ret);
+                    const float cl = __fmul_rn(dc, dc);
+                    m = fmaxf(u, cl);
+                    // inside the range both branches have the derivative 2 (v - ret); outside, the clipped branch has none
+                    const bool inside = dv >= -a.clip_coef && dv <= a.clip_coef;
+                    if (!inside) g = (u > cl) ? g : ((u == cl) ? du : 0.0f);
+                }
+                vsum = __fadd_rn(vsum, m);
+            }
+            L.dout[r * n.R + k] = __fmul_rn(g, gscale);
+        }
+        L.rs[r * PPO_NPART + 1] = vsum;
+    }
+    __syncthreads();
+    ppo_mlp_backward(L, n, n.c, p, part, n.R);
+
+    // ---- actor: forward, log-prob, ratio, policy loss (mo_ppo.py:513-533) and its gradient, backward
+    ppo_mlp_forward(L, n, n.a, p, n.A);
+    if (tid < PPO_TB) {
+        const int r = tid;
+        float pg = 0.0f, nlr = 0.0f, kl = 0.0f, cf = 0.0f, dlp = 0.0f;
+        if (r < valid) {
+            float lp = 0.0f;
+            for (int k = 0; k < n.A; ++k) {
+                const float sd = expf(p[n.oLs + k]);
+                const float diff = __fsub_rn(L.act[r * n.A + k], L.out[r * n.A + k]);
+                const float t = __fdiv_rn(-__fmul_rn(diff, diff), __fmul_rn(2.0f, __fmul_rn(sd, sd)));
+                lp = __fadd_rn(lp, __fsub_rn(__fsub_rn(t, logf(sd)), PPO_HALF_LOG_2PI));
+            }
+            const float logratio = __fsub_rn(lp, L.row[r * 4]);
+            const float ratio = expf(logratio);
+            float adv = L.row[r * 4 + 1];
+            if (a.norm_adv) adv = __fdiv_rn(__fsub_rn(adv, L.stat[0]), L.stat[1]);
+            const float pg1 = __fmul_rn(-adv, ratio);
+            const float pg2 = __fmul_rn(-adv, fminf(fmaxf(ratio, a.clip_lo), a.clip_hi));
+            pg = fmaxf(pg1, pg2);
+            // torch.max splits a tie evenly: inside the clip range both branches are the same number with the derivative -adv;
+            // outside, the clipped branch has none
+            const bool inside = ratio >= a.clip_lo && ratio <= a.clip_hi;
+            const float dratio = (inside || pg1 > pg2) ? -adv : 0.0f;
+            dlp = __fmul_rn(__fmul_rn(dratio, ratio), a.inv_M);
+            nlr = -logratio;
+            kl = __fsub_rn(__fsub_rn(ratio, 1.0f), logratio);
+            cf = (fabsf(__fsub_rn(ratio, 1.0f)) > a.clip_coef) ? 1.0f : 0.0f;
+        }
+        L.row[r * 4 + 2] = dlp;
+        L.rs[r * PPO_NPART] = pg;
+        L.rs[r * PPO_NPART + 2] = nlr;
+        L.rs[r * PPO_NPART + 3] = kl;
+        L.rs[r * PPO_NPART + 4] = cf;
+    }
+    __syncthreads();
+    // d newlogprob / d mean_k = (action - mean) / var;  d / d logstd_k = (action - mean)^2 / var - 1
+    for (int o = tid; o < PPO_TB * n.A; o += PPO_THREADS) {
+        const int r = o / n.A, k = o - r * n.A;
+        const float sd = expf(p[n.oLs + k]);
+        const float var = __fmul_rn(sd, sd);
+        const float diff = __fsub_rn(L.act[o], L.out[o]);
+        const float dlp = L.row[r * 4 + 2];
+        L.dout[o] = __fmul_rn(dlp, __fdiv_rn(diff, var));
+        L.act[o] = __fmul_rn(dlp, __fsub_rn(__fdiv_rn(__fmul_rn(diff, diff), var), 1.0f));
+    }
+    __syncthreads();
+    pcn_db(part + n.oLs, L.act, n.A, n.A);            // (the entropy's share, -ent_coef per entry, is added once by the last workgroup)
+    if (tid < PPO_NPART) {
+        float s = 0.0f;
+        for (int r = 0; r < PPO_TB; ++r) s = __fadd_rn(s, L.rs[r * PPO_NPART + tid]);
+        a.lpart[tile * PPO_NPART + tid] = s;
+    }
+    ppo_mlp_backward(L, n, n.a, p, part, n.A);
+
+    // ---- the last workgroup to arrive owns the step
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned int prev = atomicAdd(a.ticket, 1u);
+        L.last = (prev + 1u == (unsigned int)a.ntiles) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!L.last) return;
+    __threadfence();
+
+    // the gradient: partials summed in tile order (four loads in flight, added in order), kept in tile 0's slot
+    float* grad = a.part;
+    for (int t = 0; t < n.ntensors; ++t) {
+        {
+            float sq = 0.0f;
+            for (int q = n.tstart[t] + tid; q < n.tstart[t + 1]; q += PPO_THREADS) {
+                float g = a.part[q];
+                int tl = 1;
+                for (; tl + 4 <= a.ntiles; tl += 4) {
+                    const float g0 = a.part[(size_t)tl * n.P + q], g1 = a.part[(size_t)(tl + 1) * n.P + q];
+                    const float g2 = a.part[(size_t)(tl + 2) * n.P + q], g3 = a.part[(size_t)(tl + 3) * n.P + q];
+                    g = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(g, g0), g1), g2), g3);
+                }
+                for (; tl < a.ntiles; ++tl) g = __fadd_rn(g, a.part[(size_t)tl * n.P + q]);
+                if (t == 0) g = __fsub_rn(g, a.ent_coef);      // d(-ent_coef * entropy) / d logstd_k
+                grad[q] = g;
+                sq = fmaf(g, g, sq);
+            }
+            L.w[t * PPO_THREADS + tid] = sq;
+        }
+    }
+    __syncthreads();
+    // clip_grad_norm_ (mo_ppo.py:553): the 2-norm of the per-tensor 2-norms; scale = max_norm / (total + 1e-6) clamped to 1
+    if (tid < n.ntensors) {
+        float s = 0.0f;
+        for (int i = 0; i < PPO_THREADS; ++i) s = __fadd_rn(s, L.w[tid * PPO_THREADS + i]);
+        L.red[tid] = __fsqrt_rn(s);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.0f;
+        for (int t = 0; t < n.ntensors; ++t) s = fmaf(L.red[t], L.red[t], s);
+        const float total = __fsqrt_rn(s);
+        L.stat[2] = fminf(__fdiv_rn(a.max_grad_norm, __fadd_rn(total, 1e-6f)), 1.0f);
+        L.stat[3] = total;
+        *a.ticket = 0u;                                        // re-armed for the next launch on the stream
+        float ls[PPO_NPART];
+        for (int i = 0; i < PPO_NPART; ++i) ls[i] = 0.0f;
+        for (int t = 0; t < a.ntiles; ++t)
+            for (int i = 0; i < PPO_NPART; ++i) ls[i] = __fadd_rn(ls[i], a.lpart[t * PPO_NPART + i]);
+        float ent = 0.0f;                                      // Normal.entropy(): 0.5 + 0.5 log(2 pi) + log(scale), the same in every row
+        for (int k = 0; k < n.A; ++k) ent = __fadd_rn(ent, __fadd_rn(__fadd_rn(0.5f, PPO_HALF_LOG_2PI), logf(expf(p[n.oLs + k]))));
+        const float pg = __fdiv_rn(ls[0], a.fM), v = __fmul_rn(0.5f, __fdiv_rn(ls[1], a.fMR));
+        a.stats_out[0] = __fadd_rn(__fsub_rn(pg, __fmul_rn(a.ent_coef, ent)), __fmul_rn(v, a.vf_coef));
+        a.stats_out[1] = pg;
+        a.stats_out[2] = v;
+        a.stats_out[3] = ent;
+        a.stats_out[4] = __fdiv_rn(ls[2], a.fM);
+        a.stats_out[5] = __fdiv_rn(ls[3], a.fM);
+        a.stats_out[6] = __fdiv_rn(ls[4], a.fM);
+        a.stats_out[7] = total;
+    }
+    __syncthreads();
+    const float scale = L.stat[2];
+    // torch _single_tensor_adam with eps 1e-5 (mo_ppo.py:331, 554): lerp_, mul_ + addcmul_, addcdiv_
+    for (int q = tid; q < n.P; q += PPO_THREADS) {
+        const float g = __fmul_rn(grad[q], scale);
+        float m = a.exp_avg[q], v = a.exp_avg_sq[q];
+        m = fmaf(a.one_minus_b1, __fsub_rn(g, m), m);
+        v = __fadd_rn(__fmul_rn(v, a.b2), __fmul_rn(__fmul_rn(a.one_minus_b2, g), g));
+        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), a.bc2_sqrt), a.eps);
+        a.params[q] = __fadd_rn(a.params[q], __fmul_rn(a.neg_step_size, __fdiv_rn(m, denom)));
+        a.exp_avg[q] = m;
+        a.exp_avg_sq[q] = v;
+    }
+}
+
+}  // namespace morl

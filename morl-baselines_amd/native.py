@@ -264,6 +264,14 @@ _SIGNATURES = {
     "morl_pcn_set_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "morl_pcn_update_n": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 4),
     "morl_pcn_forward": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]),
+    "morl_ppo_param_count": (C.c_int64, [C.c_int] * 6),
+    "morl_ppo_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 7),
+    "morl_ppo_destroy": (C.c_int, [C.c_void_p]),
+    "morl_ppo_set_rollout": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]),
+    "morl_ppo_gae": (C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 3),
+    "morl_ppo_update_n": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int] + [C.c_double] * 4 +
+                          [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "morl_ppo_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

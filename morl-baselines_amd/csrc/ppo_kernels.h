@@ -1,5 +1,6 @@
 // Multi-objective PPO (single_policy/ser/mo_ppo.py): one minibatch step of MOPPO.update() (mo_ppo.py:509-554) as ONE launch, the
-// reverse scan of __compute_advantages (mo_ppo.py:439-476) and the no-grad get_action_and_value (mo_ppo.py:215-235).  fp32.
+// reverse scan of __compute_advantages (mo_ppo.py:439-476) and the no-grad get_action_and_value (mo_ppo.py:215-235).  fp32; the
+// terms of a row's log-prob are added in double (ppo_logprob_add).
 //
 //   critic:      obs -> hidden (Tanh) -> [R]          actor_mean: obs -> hidden (Tanh) -> [A]          actor_logstd [1][A]
 //   newlogprob = sum_a Normal(mean, exp(logstd)).log_prob(action),  ratio = exp(newlogprob - old log-prob)
@@ -28,6 +29,7 @@ constexpr int PPO_MAX_TENSORS = 13;     // actor_logstd + 2 networks x 3 layers 
 constexpr int PPO_NSTATS = 8;           // loss, pg_loss, v_loss, entropy, old_approx_kl, approx_kl, clipfrac, grad_norm
 constexpr int PPO_NPART = 5;            // per-tile sums: pg, v, -logratio, (ratio - 1) - logratio, clipped rows
 constexpr float PPO_HALF_LOG_2PI = 0.91893853320467274178f;   // log(sqrt(2 pi))
+constexpr double PPO_HALF_LOG_2PI_D = 0.91893853320467274178;
 static_assert(PPO_MAX_H <= PCN_MAX_H && PPO_THREADS == 256 && PPO_TB == 16, "pcn_dense / pcn_dw are shared");
 
 // one of the two MLPs as a map into the flat parameter vector; with one hidden layer W1 / b1 are absent (H2 == H1, nh == 1)
@@ -62,6 +64,14 @@ struct PpoLds {
 static_assert(sizeof(PpoLds) <= 64 * 1024, "PPO tile state must fit 64 KB of static LDS");
 static_assert(PPO_MAX_TENSORS * PPO_THREADS <= PCN_MAX_H * PCN_WLD, "per-tensor sums of squares reuse the weight stage");
 static_assert(32 * (PPO_MAX_H + 1) <= PCN_MAX_H * PCN_WLD, "transposed stage: 32 rows of a weight");
+
+// A row's log-prob is a sum of up to 32 terms of O(1) each, and the statistics approx_kl / old_approx_kl are means of its
+// DIFFERENCE to the old log-prob: summed in float, the running sum's rounding (an ulp of up to 4e-6 per term at action_dim 31)
+// and the 31-fold rounding of log(sqrt(2 pi)) are 1e-6 of those means.  The terms are formed in float as torch forms them and
+// added in double; the sum is rounded to float once, so an unchanged policy still reproduces its stored log-prob bit for bit.
+__device__ __forceinline__ double ppo_logprob_add(double lp, float t, float sd) {
+    return lp + (((double)t - (double)logf(sd)) - PPO_HALF_LOG_2PI_D);
+}
 
 // forward of one MLP on the tile's rows in L.x: tanh activations in L.h1 (/ L.h2), the head's output in L.out [16][N]
 __device__ __forceinline__ void ppo_mlp_forward(PpoLds& L, const PpoNet& n, const PpoMlp& m, const float* __restrict__ p, int N) {
@@ -175,17 +185,17 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_forward_kernel(PpoNet 
     ppo_mlp_forward(L, n, n.a, params, n.A);
     if (tid < PPO_TB && row0 + tid < rows) {
         const int r = tid;
-        float lp = 0.0f;
+        double lp = 0.0;
         for (int k = 0; k < n.A; ++k) {
             const float sd = expf(params[n.oLs + k]), mean = L.out[r * n.A + k];
             const float act = __fadd_rn(mean, __fmul_rn(sd, L.act[r * n.A + k]));        // Normal.sample(): loc + eps * scale
             const float diff = __fsub_rn(act, mean);
             const float var = __fmul_rn(sd, sd);
             const float t = __fdiv_rn(-__fmul_rn(diff, diff), __fmul_rn(2.0f, var));
-            lp = __fadd_rn(lp, __fsub_rn(__fsub_rn(t, logf(sd)), PPO_HALF_LOG_2PI));
+            lp = ppo_logprob_add(lp, t, sd);
             action_out[(size_t)(row0 + r) * n.A + k] = act;
         }
-        logprob_out[row0 + r] = lp;
+        logprob_out[row0 + r] = (float)lp;
     }
 }
 
@@ -393,14 +403,14 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
         const int r = tid;
         float pg = 0.0f, nlr = 0.0f, kl = 0.0f, cf = 0.0f, dlp = 0.0f;
         if (r < valid) {
-            float lp = 0.0f;
+            double lp = 0.0;
             for (int k = 0; k < n.A; ++k) {
                 const float sd = expf(p[n.oLs + k]);
                 const float diff = __fsub_rn(L.act[r * n.A + k], L.out[r * n.A + k]);
                 const float t = __fdiv_rn(-__fmul_rn(diff, diff), __fmul_rn(2.0f, __fmul_rn(sd, sd)));
-                lp = __fadd_rn(lp, __fsub_rn(__fsub_rn(t, logf(sd)), PPO_HALF_LOG_2PI));
+                lp = ppo_logprob_add(lp, t, sd);
             }
-            const float logratio = __fsub_rn(lp, L.row[r * 4]);
+            const float logratio = __fsub_rn((float)lp, L.row[r * 4]);
             const float ratio = expf(logratio);
             float adv = L.row[r * 4 + 1];
             if (a.norm_adv) adv = __fdiv_rn(__fsub_rn(adv, L.stat[0]), L.stat[1]);

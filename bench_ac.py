@@ -38,6 +38,7 @@ SHAPES = {  # obs dim, action dim, objectives of the environments BASELINE.json 
     "ens": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (GPI-PD Dyna model: one-hot action in, next-obs delta + reward out)"),
     "pcn": dict(D=9, Ad=4, R=2, env="treasure-line (discrete head) / mo-hopper-v4 shapes 11-3-3 (continuous head)"),
     "ppo": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
+    "pgmorl": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
 }
 ARCH = [256, 256]
 B = 128
@@ -565,6 +566,153 @@ def bench_ppo(a):
     print(json.dumps(out), file=RESULT_OUT, flush=True)
 
 
+def bench_pgmorl(a):
+    """PGMORL's population (multi_policy/pgmorl/pgmorl.py, ``pop_size`` MOPPO learners) at the ``ppo`` row's shapes: every learner
+    has its own parameters, rollout and shuffles.  Three pairs, each timed in the same process in interleaved windows (five per leg,
+    the figure is the median window): the 320 minibatch steps of an iteration as ONE ``morl_ppo_update_n_pop`` call against P
+    back-to-back ``morl_ppo_update_n`` calls; ``morl_ppo_gae_pop`` against P ``morl_ppo_gae`` calls; one lock-step acting step
+    (``morl_ppo_forward_pop`` on 4 rows per learner and one host read) against P ``morl_ppo_forward`` calls with a read each.
+    Before anything is timed both legs run one update from the same start and must leave bit-identical parameters."""
+    import ctypes as C
+
+    from morl_baselines_amd.mo_ppo import MOPPONet
+    from morl_baselines_amd.native import load_library
+
+    lib, dev = load_library(), th.device("cuda", 0)
+    P = a.pop or 6
+    T, E, D, A, R, hidden = 2048, 4, 17, 6, 2, [64, 64]
+    epochs, n_mb, lr, gamma, lam = 10, 32, 3e-4, 0.995, 0.95
+    rows, M, n_steps = T * E, T * E // n_mb, epochs * n_mb
+    loops = max(1, a.steps)
+    ptrs = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
+    th.manual_seed(0)
+    g = th.Generator().manual_seed(1)
+    rng = np.random.default_rng(0)
+    to = lambda t: t.to(dev).contiguous()  # noqa: E731
+    p0, roll, idx, nv, nd, w = [], [], [], [], [], []
+    for i in range(P):
+        net = MOPPONet((D,), (A,), R, hidden)
+        p0.append(to(th.cat([p.detach().reshape(-1) for p in net.parameters()])))
+        obs, act = th.randn(rows, D, generator=g), th.randn(rows, A, generator=g)
+        # (old log-probs near those of a unit-variance policy with a small mean, old values near the critic's: steps of ordinary size)
+        logp = -0.5 * (act ** 2).sum(1) - A * 0.9189385 + 0.02 * th.randn(rows, generator=g)
+        roll.append([to(t) for t in (obs, act, logp, th.randn(rows, R, generator=g), (th.rand(rows, generator=g) < 0.001).float(),
+                                     0.1 * th.randn(rows, R, generator=g))])
+        nv.append(to(th.randn(E, R, generator=g)))
+        nd.append(to(th.zeros(E)))
+        w.append(to(th.tensor([i / max(P - 1, 1), 1.0 - i / max(P - 1, 1)])))
+        b_inds, steps = np.arange(rows), []
+        for _ in range(epochs):
+            rng.shuffle(b_inds)
+            steps += [b_inds[s_:s_ + M].copy() for s_ in range(0, rows, M)]
+        idx.append(th.tensor(np.stack(steps).astype(np.int32)).to(dev))
+    stream = lib.stream_of(p0[0])
+
+    def make_leg():
+        hs = []
+        for i in range(P):
+            h = C.c_void_p()
+            lib.check(lib.lib.morl_ppo_create(C.byref(h), D, A, R, 2, hidden[0], hidden[1], M))
+            lib.check(lib.lib.morl_ppo_set_rollout(h, *[t.data_ptr() for t in roll[i]], T, E, stream))
+            hs.append(h.value)
+        return dict(h=hs, p=[t.clone() for t in p0], m=[th.zeros_like(t) for t in p0], v=[th.zeros_like(t) for t in p0], steps=0,
+                    stats=[th.zeros(n_steps, 8, device=dev) for _ in range(P)], ret=[th.zeros(rows, R, device=dev) for _ in range(P)],
+                    adv=[th.zeros(rows, device=dev) for _ in range(P)])
+
+    pop, seq = make_leg(), make_leg()
+    pop_h = (C.c_void_p * P)(*pop["h"])
+
+    def pop_gae():
+        lib.check(lib.lib.morl_ppo_gae_pop(P, pop_h, ptrs(nv), ptrs(nd), ptrs(w), gamma, lam, 1, ptrs(pop["ret"]), ptrs(pop["adv"]), stream))
+
+    def seq_gae():
+        for i in range(P):
+            lib.check(lib.lib.morl_ppo_gae(seq["h"][i], nv[i].data_ptr(), nd[i].data_ptr(), w[i].data_ptr(), gamma, lam, 1,
+                                           seq["ret"][i].data_ptr(), seq["adv"][i].data_ptr(), stream))
+
+    def pop_update():
+        lib.check(lib.lib.morl_ppo_update_n_pop(P, pop_h, ptrs(pop["p"]), ptrs(pop["m"]), ptrs(pop["v"]), n_steps, ptrs(idx), M,
+                                                (C.c_double * P)(*[lr] * P), (C.c_int * P)(*[pop["steps"]] * P), 0.2, 0.0, 0.5, 0.5, 1, 1,
+                                                ptrs(pop["stats"]), stream))
+        pop["steps"] += n_steps
+
+    def seq_update():
+        for i in range(P):
+            lib.check(lib.lib.morl_ppo_update_n(seq["h"][i], seq["p"][i].data_ptr(), seq["m"][i].data_ptr(), seq["v"][i].data_ptr(),
+                                                n_steps, idx[i].data_ptr(), M, lr, seq["steps"], 0.2, 0.0, 0.5, 0.5, 1, 1,
+                                                seq["stats"][i].data_ptr(), stream))
+        seq["steps"] += n_steps
+
+    obs_a, eps_a = to(th.randn(P, E, D, generator=g)), to(th.randn(P, E, A, generator=g))
+    act_o, lp_o, val_o = th.zeros(P, E, A, device=dev), th.zeros(P, E, device=dev), th.zeros(P, E, R, device=dev)
+    each = lambda t: ptrs([t[i] for i in range(P)])  # noqa: E731
+
+    def pop_act():
+        lib.check(lib.lib.morl_ppo_forward_pop(P, pop_h, ptrs(pop["p"]), each(obs_a), each(eps_a), E, 0, each(act_o), each(lp_o),
+                                               each(val_o), stream))
+        return act_o.cpu()
+
+    def seq_act():
+        out = []
+        for i in range(P):
+            lib.check(lib.lib.morl_ppo_forward(seq["h"][i], seq["p"][i].data_ptr(), obs_a[i].data_ptr(), eps_a[i].data_ptr(), E, 0,
+                                               act_o[i].data_ptr(), lp_o[i].data_ptr(), val_o[i].data_ptr(), stream))
+            out.append(act_o[i].cpu())
+        return out
+
+    # same inputs, same start: both legs must leave the same bits before anything is timed
+    pop_gae()
+    seq_gae()
+    pop_update()
+    seq_update()
+    th.cuda.synchronize()
+    same = all(th.equal(x, y) for k in ("p", "m", "v", "stats", "ret", "adv") for x, y in zip(pop[k], seq[k]))
+    if not same:
+        raise SystemExit("bench_pgmorl: the population call and the sequential calls left different bits")
+    finite = all(bool(th.isfinite(s).all()) for s in pop["stats"])
+    a_pop, a_seq = pop_act(), seq_act()
+    if not all(th.equal(a_pop[i], a_seq[i]) for i in range(P)):
+        raise SystemExit("bench_pgmorl: forward_pop and forward gave different actions")
+    for _ in range(max(1, a.warmup // 10)):
+        pop_update()
+        seq_update()
+    th.cuda.synchronize()
+    t = {k: [] for k in ("pop", "seq", "pop_gae", "seq_gae", "pop_act", "seq_act")}
+    for _ in range(5):
+        for name, fn, reps, per in (("pop", pop_update, loops, n_steps), ("seq", seq_update, loops, n_steps), ("pop_gae", pop_gae, loops, 1),
+                                    ("seq_gae", seq_gae, loops, 1), ("pop_act", pop_act, 20 * loops, 1), ("seq_act", seq_act, 20 * loops, 1)):
+            th.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            th.cuda.synchronize()
+            t[name].append((time.perf_counter() - t0) * 1e3 / (reps * per))
+    th.cuda.synchronize()
+    same_after = all(th.equal(x, y) for k in ("p", "m", "v") for x, y in zip(pop[k], seq[k]))
+    for h in pop["h"] + seq["h"]:
+        lib.lib.morl_ppo_destroy(h)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    spread = lambda v: (max(v) - min(v)) / float(np.median(v))  # noqa: E731
+    pair = lambda p_, s_: {"population_ms": med[p_], "sequential_ms": med[s_], "sequential_over_population": med[s_] / med[p_],  # noqa: E731
+                           "population_windows_ms": t[p_], "sequential_windows_ms": t[s_], "sequential_window_spread": spread(t[s_])}
+    out = {"metric": f"PGMORL population minibatch steps/sec ({P} learners per step, one launch)", "value": 1e3 / med["pop"],
+           "unit": "population steps/s", "n_gpus": 1, "steps": loops, "warmup": a.warmup, "ms_per_step": med["pop"],
+           "higher_is_better": True, "vs_baseline": med["seq"] / med["pop"], "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"PGMORL's {P} MOPPO learners at its defaults: each an 8192-row rollout (4 envs x 2048 steps), 10 epochs x "
+                                  "32 minibatches of 256, net [64, 64], shapes 17-6-2 (mo-halfcheetah), own parameters / rollout / "
+                                  "shuffles; one morl_ppo_update_n_pop call per iteration; baseline: the same steps as P back-to-back "
+                                  "morl_ppo_update_n calls (the parent's way), same process, interleaved windows"},
+           "shape": dict(pop=P, obs_dim=D, action_dim=A, reward_dim=R, hidden=hidden, rollout_rows=rows, minibatch=M,
+                         steps_per_update=n_steps, workgroups_per_launch=P * ((M + 15) // 16)),
+           "update": pair("pop", "seq"), "gae": pair("pop_gae", "seq_gae"), "acting": pair("pop_act", "seq_act"),
+           "bit_identical_before_timing": same, "bit_identical_after_timing": same_after, "statistics_finite": finite,
+           "loops_per_window": {"update": loops, "gae": loops, "acting": 20 * loops},
+           "roofline": {"bound": "latency", "kernel": "ppo_pop_step_kernel", "achieved": None, "peak": None, "unit": None, "frac": None,
+                        "traffic": None, "note": "a step is a chain of dependent launches of one tile's latency each; the population "
+                                                 "fills idle CUs, it does not shorten the chain"}}
+    print(json.dumps(out), file=RESULT_OUT, flush=True)
+
+
 def _claim_stdout():
     """stdout must carry exactly ONE line, rank 0's JSON: C libraries (RCCL prints a version banner to stdout, flushed
     at exit, i.e. after the JSON) and the other ranks are moved to stderr; the result is written to the saved descriptor."""
@@ -680,6 +828,8 @@ def main():
         return bench_pcn(a)
     if a.workload == "ppo":
         return bench_ppo(a)
+    if a.workload == "pgmorl":
+        return bench_pgmorl(a)
     from morl_baselines_amd.ac_engine import ALGO_CAPQL, ALGO_MOSAC, ALGO_TD3, ACEngine
 
     wl, shp = a.workload, SHAPES[a.workload]

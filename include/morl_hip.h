@@ -884,6 +884,31 @@ int morl_ppo_update_n(morl_ppo_ctx* ctx, float* params, float* exp_avg, float* e
 int morl_ppo_forward(morl_ppo_ctx* ctx, const float* params, const float* obs, const float* eps, int rows, int value_only,
                      float* action_out, float* logprob_out, float* value_out, void* stream);
 
+/* ---- a population of P independent learners (PGMORL's pop_size MOPPO agents), P >= 1 ------------------------------------------
+ * ctxs [P] are existing handles, all of the same network shapes and each at most once per call (a learner owns its context's
+ * ticket and partials); every other `x[]` argument is a HOST array of P device pointers (or P scalars), entry i for ctxs[i].  The
+ * learner axis is a grid axis: one launch serves up to 16 learners (larger populations: ceil(P / 16) launches), and learner i
+ * computes bit for bit what the single-learner entry computes for it.  The arrays are read before the call returns: the
+ * per-learner records travel in the kernel argument, so calls may be queued back to back on one stream without synchronising
+ * and the host arrays may be reused at once.  A refused call (MORL_ERR_ARG / MORL_ERR_STATE) launches nothing. */
+/* n steps for every learner, one launch per step (per 16 learners): idx[i] [n][M], stats_out[i] [n][8]; lr and adam_steps_done per
+ * learner; M and the coefficients shared.  Every context needs a rollout with advantages and max_minibatch >= M. */
+int morl_ppo_update_n_pop(int P, morl_ppo_ctx* const* ctxs, float* const* params, float* const* exp_avg, float* const* exp_avg_sq,
+                          int n, const int32_t* const* idx, int M, const double* lr, const int* adam_steps_done, double clip_coef,
+                          double ent_coef, double vf_coef, double max_grad_norm, int clip_vloss, int norm_adv,
+                          float* const* stats_out, void* stream);
+/* morl_ppo_forward for every learner in one launch: obs[i] [rows][D], eps[i] [rows][A], outputs per learner; rows shared.
+ * value_only != 0: eps / action_out / logprob_out may be NULL. */
+int morl_ppo_forward_pop(int P, morl_ppo_ctx* const* ctxs, const float* const* params, const float* const* obs,
+                         const float* const* eps, int rows, int value_only, float* const* action_out, float* const* logprob_out,
+                         float* const* value_out, void* stream);
+/* morl_ppo_gae for every learner in one launch: the contexts' rollouts must have the same T and E; next_value[i] [E][R],
+ * next_done[i] [E], weights[i] [R]; returns_out / advantages_out: arrays of P pointers, or NULL.  Marks every context's
+ * advantages as present. */
+int morl_ppo_gae_pop(int P, morl_ppo_ctx* const* ctxs, const float* const* next_value, const float* const* next_done,
+                     const float* const* weights, double gamma, double gae_lambda, int use_gae, float* const* returns_out,
+                     float* const* advantages_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,4 +18,7 @@ def __getattr__(name):
     if name in ("MOPPO", "MOPPONet"):
         from . import mo_ppo
         return getattr(mo_ppo, name)
+    if name == "PGMORL":
+        from .pgmorl import PGMORL
+        return PGMORL
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

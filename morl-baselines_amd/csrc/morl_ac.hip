@@ -2474,3 +2474,151 @@ extern "C" int morl_ppo_forward(morl_ppo_ctx* c, const float* params, const floa
     LAUNCH_CHECK("ppo_forward");
     return MORL_OK;
 }
+
+// ---- a population of MO-PPO learners: the learner axis is blockIdx.y, PPO_POP_CHUNK learners per launch ----------------------
+// The per-learner records are copied into the kernel argument at launch, so a call returns with nothing of its own left to
+// protect: the caller may queue the next call (with other idx / stats pointers) at once.
+static int ppo_pop_check(int P, morl_ppo_ctx* const* ctxs, const char* what) {
+    if (P < 1) return fail(MORL_ERR_ARG, "MO-PPO %s: population of %d learners", what, P);
+    if (!ctxs) return fail(MORL_ERR_ARG, "MO-PPO %s: ctxs is NULL", what);
+    for (int i = 0; i < P; ++i)
+        if (!ctxs[i]) return fail(MORL_ERR_ARG, "MO-PPO %s: ctxs[%d] is NULL", what, i);
+    std::vector<const morl_ppo_ctx*> seen(ctxs, ctxs + P);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
+        return fail(MORL_ERR_ARG, "MO-PPO %s: the same context twice in one call (two learners would share a ticket and partials)", what);
+    const PpoNet& n = ctxs[0]->n;
+    for (int i = 1; i < P; ++i) {
+        const PpoNet& m = ctxs[i]->n;
+        if (m.D != n.D || m.A != n.A || m.R != n.R || m.nh != n.nh || m.H1 != n.H1 || m.H2 != n.H2)
+            return fail(MORL_ERR_ARG, "MO-PPO %s: ctxs[%d] has other network shapes than ctxs[0]", what, i);
+    }
+    return MORL_OK;
+}
+
+template <class T>
+static int ppo_pop_ptrs(int P, T* const* a, const char* what, const char* name) {
+    if (!a) return fail(MORL_ERR_ARG, "MO-PPO %s: %s is NULL", what, name);
+    for (int i = 0; i < P; ++i)
+        if (!a[i]) return fail(MORL_ERR_ARG, "MO-PPO %s: %s[%d] is NULL", what, name, i);
+    return MORL_OK;
+}
+
+extern "C" int morl_ppo_update_n_pop(int P, morl_ppo_ctx* const* ctxs, float* const* params, float* const* exp_avg,
+                                     float* const* exp_avg_sq, int n, const int32_t* const* idx, int M, const double* lr,
+                                     const int* adam_steps_done, double clip_coef, double ent_coef, double vf_coef,
+                                     double max_grad_norm, int clip_vloss, int norm_adv, float* const* stats_out, void* stream) {
+    int rc;
+    if ((rc = ppo_pop_check(P, ctxs, "update_n_pop")) || (rc = ppo_pop_ptrs(P, params, "update_n_pop", "params")) ||
+        (rc = ppo_pop_ptrs(P, exp_avg, "update_n_pop", "exp_avg")) || (rc = ppo_pop_ptrs(P, exp_avg_sq, "update_n_pop", "exp_avg_sq")) ||
+        (rc = ppo_pop_ptrs(P, idx, "update_n_pop", "idx")) || (rc = ppo_pop_ptrs(P, stats_out, "update_n_pop", "stats_out")))
+        return rc;
+    if (!lr || !adam_steps_done) return fail(MORL_ERR_ARG, "MO-PPO update_n_pop: lr / adam_steps_done is NULL");
+    if (n < 1) return fail(MORL_ERR_ARG, "n = %d updates", n);
+    if (norm_adv && M < 2) return fail(MORL_ERR_ARG, "MO-PPO: norm_adv needs a minibatch of at least 2 rows (std of %d)", M);
+    for (int i = 0; i < P; ++i) {
+        const morl_ppo_ctx* c = ctxs[i];
+        if (M < 1 || M > c->max_minibatch)
+            return fail(MORL_ERR_STATE, "MO-PPO: minibatch %d outside 1..max_minibatch %d of ctxs[%d]", M, c->max_minibatch, i);
+        if (c->T < 1) return fail(MORL_ERR_STATE, "MO-PPO: ctxs[%d] has no rollout (morl_ppo_set_rollout)", i);
+        if (!c->have_gae) return fail(MORL_ERR_STATE, "MO-PPO: the rollout of ctxs[%d] has no advantages yet (morl_ppo_gae)", i);
+        if (adam_steps_done[i] < 0) return fail(MORL_ERR_ARG, "adam_steps_done[%d] = %d", i, adam_steps_done[i]);
+    }
+    const morl_ppo_ctx* c0 = ctxs[0];
+    PpoPopStepArgs a{};
+    a.s.n = c0->n;
+    a.s.row_w = c0->row_w;
+    a.s.M = M; a.s.ntiles = (M + PPO_TB - 1) / PPO_TB;
+    a.s.clip_lo = (float)(1.0 - clip_coef); a.s.clip_hi = (float)(1.0 + clip_coef); a.s.clip_coef = (float)clip_coef;
+    a.s.ent_coef = (float)ent_coef; a.s.vf_coef = (float)vf_coef; a.s.max_grad_norm = (float)max_grad_norm;
+    a.s.clip_vloss = clip_vloss ? 1 : 0; a.s.norm_adv = norm_adv ? 1 : 0;
+    a.s.inv_M = (float)(1.0 / M); a.s.inv_MR = (float)(1.0 / ((double)M * c0->n.R)); a.s.inv_Mm1 = M > 1 ? (float)(1.0 / (M - 1)) : 0.0f;
+    a.s.fM = (float)M; a.s.fMR = (float)((double)M * c0->n.R);
+    const double b1 = 0.9, b2 = 0.999;
+    a.s.one_minus_b1 = (float)(1.0 - b1); a.s.b2 = (float)b2; a.s.one_minus_b2 = (float)(1.0 - b2); a.s.eps = 1e-5f;
+    for (int k = 0; k < n; ++k) {
+        for (int p0 = 0; p0 < P; p0 += PPO_POP_CHUNK) {
+            const int pc = std::min(PPO_POP_CHUNK, P - p0);
+            for (int j = 0; j < pc; ++j) {
+                const int i = p0 + j;
+                const morl_ppo_ctx* c = ctxs[i];
+                const int step = adam_steps_done[i] + k + 1;
+                PpoLearner& l = a.l[j];
+                l.params = params[i]; l.exp_avg = exp_avg[i]; l.exp_avg_sq = exp_avg_sq[i];
+                l.table = c->table; l.table_rows = c->T * c->E;
+                l.idx = idx[i] + (size_t)k * M;
+                l.part = c->part; l.lpart = c->lpart; l.ticket = c->ticket;
+                l.stats_out = stats_out[i] + (size_t)k * PPO_NSTATS;
+                l.neg_step_size = (float)(-(lr[i] / (1.0 - std::pow(b1, step))));
+                l.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, step));
+            }
+            hipLaunchKernelGGL(ppo_pop_step_kernel, dim3(a.s.ntiles, pc), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
+            LAUNCH_CHECK("ppo_pop_step");
+        }
+    }
+    return MORL_OK;
+}
+
+extern "C" int morl_ppo_forward_pop(int P, morl_ppo_ctx* const* ctxs, const float* const* params, const float* const* obs,
+                                    const float* const* eps, int rows, int value_only, float* const* action_out,
+                                    float* const* logprob_out, float* const* value_out, void* stream) {
+    int rc;
+    if ((rc = ppo_pop_check(P, ctxs, "forward_pop")) || (rc = ppo_pop_ptrs(P, params, "forward_pop", "params")) ||
+        (rc = ppo_pop_ptrs(P, obs, "forward_pop", "obs")) || (rc = ppo_pop_ptrs(P, value_out, "forward_pop", "value_out")))
+        return rc;
+    if (!value_only && ((rc = ppo_pop_ptrs(P, eps, "forward_pop", "eps")) || (rc = ppo_pop_ptrs(P, action_out, "forward_pop", "action_out")) ||
+                        (rc = ppo_pop_ptrs(P, logprob_out, "forward_pop", "logprob_out"))))
+        return rc;
+    if (rows < 1) return fail(MORL_ERR_ARG, "MO-PPO: rows = %d", rows);
+    PpoPopFwdArgs a{};
+    a.n = ctxs[0]->n;
+    a.rows = rows; a.value_only = value_only ? 1 : 0;
+    for (int p0 = 0; p0 < P; p0 += PPO_POP_CHUNK) {
+        const int pc = std::min(PPO_POP_CHUNK, P - p0);
+        for (int j = 0; j < pc; ++j) {
+            const int i = p0 + j;
+            PpoFwdLearner& l = a.l[j];
+            l.params = params[i]; l.obs = obs[i]; l.value_out = value_out[i];
+            l.eps = value_only ? nullptr : eps[i];
+            l.action_out = value_only ? nullptr : action_out[i];
+            l.logprob_out = value_only ? nullptr : logprob_out[i];
+        }
+        hipLaunchKernelGGL(ppo_pop_forward_kernel, dim3((rows + PPO_TB - 1) / PPO_TB, pc), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
+        LAUNCH_CHECK("ppo_pop_forward");
+    }
+    return MORL_OK;
+}
+
+extern "C" int morl_ppo_gae_pop(int P, morl_ppo_ctx* const* ctxs, const float* const* next_value, const float* const* next_done,
+                                const float* const* weights, double gamma, double gae_lambda, int use_gae,
+                                float* const* returns_out, float* const* advantages_out, void* stream) {
+    int rc;
+    if ((rc = ppo_pop_check(P, ctxs, "gae_pop")) || (rc = ppo_pop_ptrs(P, next_value, "gae_pop", "next_value")) ||
+        (rc = ppo_pop_ptrs(P, next_done, "gae_pop", "next_done")) || (rc = ppo_pop_ptrs(P, weights, "gae_pop", "weights")))
+        return rc;
+    for (int i = 0; i < P; ++i) {
+        if (ctxs[i]->T < 1) return fail(MORL_ERR_STATE, "MO-PPO: ctxs[%d] has no rollout (morl_ppo_set_rollout)", i);
+        if (ctxs[i]->T != ctxs[0]->T || ctxs[i]->E != ctxs[0]->E)
+            return fail(MORL_ERR_STATE, "MO-PPO gae_pop: the rollout of ctxs[%d] is %d x %d, that of ctxs[0] %d x %d", i, ctxs[i]->T,
+                        ctxs[i]->E, ctxs[0]->T, ctxs[0]->E);
+    }
+    const morl_ppo_ctx* c0 = ctxs[0];
+    PpoPopGaeArgs a{};
+    a.T = c0->T; a.E = c0->E; a.R = c0->n.R; a.row_w = c0->row_w; a.adv_col = c0->n.D + c0->n.A + 1;
+    a.use_gae = use_gae ? 1 : 0; a.gamma = (float)gamma; a.gamma_lambda = (float)(gamma * gae_lambda);
+    for (int p0 = 0; p0 < P; p0 += PPO_POP_CHUNK) {
+        const int pc = std::min(PPO_POP_CHUNK, P - p0);
+        for (int j = 0; j < pc; ++j) {
+            const int i = p0 + j;
+            PpoGaeLearner& l = a.l[j];
+            l.table = ctxs[i]->table; l.rewards = ctxs[i]->rewards; l.dones = ctxs[i]->dones;
+            l.next_value = next_value[i]; l.next_done = next_done[i]; l.weights = weights[i];
+            l.returns_out = returns_out ? returns_out[i] : nullptr;
+            l.adv_out = advantages_out ? advantages_out[i] : nullptr;
+        }
+        hipLaunchKernelGGL(ppo_pop_gae_kernel, dim3((a.E + 63) / 64, pc), dim3(64), 0, (hipStream_t)stream, a);
+        LAUNCH_CHECK("ppo_pop_gae");
+    }
+    for (int i = 0; i < P; ++i) ctxs[i]->have_gae = 1;
+    return MORL_OK;
+}

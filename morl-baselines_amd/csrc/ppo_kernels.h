@@ -160,14 +160,12 @@ __device__ __forceinline__ float ppo_tree_sum(float* red, float v) {
 // ---------------------------------------------------------------------------------------------------------------------
 // no-grad get_action_and_value / get_value
 // ---------------------------------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(PPO_THREADS) void ppo_forward_kernel(PpoNet n, const float* __restrict__ params,
-                                                                        const float* __restrict__ obs,
-                                                                        const float* __restrict__ eps, int rows, int value_only,
-                                                                        float* __restrict__ action_out,
-                                                                        float* __restrict__ logprob_out,
-                                                                        float* __restrict__ value_out) {
-    __shared__ PpoLds L;
-    const int tid = (int)threadIdx.x, row0 = (int)blockIdx.x * PPO_TB;
+// the body of ppo_forward_kernel / ppo_pop_forward_kernel: rows [tile * 16, tile * 16 + 16) of one learner
+__device__ __forceinline__ void ppo_forward_tile(PpoLds& L, const PpoNet& n, int tile, const float* __restrict__ params,
+                                                 const float* __restrict__ obs, const float* __restrict__ eps, int rows,
+                                                 int value_only, float* __restrict__ action_out, float* __restrict__ logprob_out,
+                                                 float* __restrict__ value_out) {
+    const int tid = (int)threadIdx.x, row0 = tile * PPO_TB;
     for (int o = tid; o < PPO_TB * n.D; o += PPO_THREADS) {
         const int r = o / n.D, d = o - r * n.D;
         L.x[o] = (row0 + r < rows) ? obs[(size_t)(row0 + r) * n.D + d] : 0.0f;
@@ -199,6 +197,35 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_forward_kernel(PpoNet 
     }
 }
 
+
+static __global__ __launch_bounds__(PPO_THREADS) void ppo_forward_kernel(PpoNet n, const float* __restrict__ params,
+                                                                        const float* __restrict__ obs,
+                                                                        const float* __restrict__ eps, int rows, int value_only,
+                                                                        float* __restrict__ action_out,
+                                                                        float* __restrict__ logprob_out,
+                                                                        float* __restrict__ value_out) {
+    __shared__ PpoLds L;
+    ppo_forward_tile(L, n, (int)blockIdx.x, params, obs, eps, rows, value_only, action_out, logprob_out, value_out);
+}
+
+// One launch for a population: blockIdx.y is the learner, a chunk of at most PPO_POP_CHUNK of them.  The records travel BY VALUE
+// in the kernel argument, so a launch that is still queued keeps its own copy whatever the host does next.
+constexpr int PPO_POP_CHUNK = 16;
+struct PpoFwdLearner {
+    const float *params, *obs, *eps;
+    float *action_out, *logprob_out, *value_out;
+};
+struct PpoPopFwdArgs {
+    PpoNet n;
+    int rows, value_only;
+    PpoFwdLearner l[PPO_POP_CHUNK];
+};
+static __global__ __launch_bounds__(PPO_THREADS) void ppo_pop_forward_kernel(PpoPopFwdArgs a) {
+    __shared__ PpoLds L;
+    const PpoFwdLearner& l = a.l[blockIdx.y];
+    ppo_forward_tile(L, a.n, (int)blockIdx.x, l.params, l.obs, l.eps, a.rows, a.value_only, l.action_out, l.logprob_out, l.value_out);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // rollout table: one row per (step, env):  obs [D] | action [A] | old log-prob | scalarised advantage | returns [R] | old values [R]
 // ---------------------------------------------------------------------------------------------------------------------
@@ -222,11 +249,11 @@ static __global__ __launch_bounds__(256) void ppo_pack_kernel(int D, int A, int 
 //   gae:  delta = r + gamma * next_v * nonterminal - v;  last = delta + (gamma * gae_lambda) * nonterminal * last;  returns = last + v
 //   else: returns = r + gamma * nonterminal * next_return;  advantage = returns - v
 // and scalarises: advantages @ weights, summed over the objectives in index order
-static __global__ __launch_bounds__(64) void ppo_gae_kernel(int T, int E, int R, int row_w, int adv_col, float* __restrict__ table,
-                                                            const float* __restrict__ rewards, const float* __restrict__ dones,
-                                                            const float* __restrict__ next_value, const float* __restrict__ next_done,
-                                                            const float* __restrict__ weights, float gamma, float gamma_lambda,
-                                                            int use_gae, float* __restrict__ returns_out, float* __restrict__ adv_out) {
+__device__ __forceinline__ void ppo_gae_scan(int T, int E, int R, int row_w, int adv_col, float* __restrict__ table,
+                                             const float* __restrict__ rewards, const float* __restrict__ dones,
+                                             const float* __restrict__ next_value, const float* __restrict__ next_done,
+                                             const float* __restrict__ weights, float gamma, float gamma_lambda, int use_gae,
+                                             float* __restrict__ returns_out, float* __restrict__ adv_out) {
     const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (e >= E) return;
     float carry[PPO_MAX_R], nextv[PPO_MAX_R];
@@ -268,6 +295,32 @@ static __global__ __launch_bounds__(64) void ppo_gae_kernel(int T, int E, int R,
     }
 }
 
+
+static __global__ __launch_bounds__(64) void ppo_gae_kernel(int T, int E, int R, int row_w, int adv_col, float* __restrict__ table,
+                                                            const float* __restrict__ rewards, const float* __restrict__ dones,
+                                                            const float* __restrict__ next_value, const float* __restrict__ next_done,
+                                                            const float* __restrict__ weights, float gamma, float gamma_lambda,
+                                                            int use_gae, float* __restrict__ returns_out, float* __restrict__ adv_out) {
+    ppo_gae_scan(T, E, R, row_w, adv_col, table, rewards, dones, next_value, next_done, weights, gamma, gamma_lambda, use_gae,
+                 returns_out, adv_out);
+}
+
+struct PpoGaeLearner {
+    float* table;
+    const float *rewards, *dones, *next_value, *next_done, *weights;
+    float *returns_out, *adv_out;
+};
+struct PpoPopGaeArgs {
+    int T, E, R, row_w, adv_col, use_gae;
+    float gamma, gamma_lambda;
+    PpoGaeLearner l[PPO_POP_CHUNK];
+};
+static __global__ __launch_bounds__(64) void ppo_pop_gae_kernel(PpoPopGaeArgs a) {
+    const PpoGaeLearner& l = a.l[blockIdx.y];
+    ppo_gae_scan(a.T, a.E, a.R, a.row_w, a.adv_col, l.table, l.rewards, l.dones, l.next_value, l.next_done, l.weights, a.gamma,
+                 a.gamma_lambda, a.use_gae, l.returns_out, l.adv_out);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // one minibatch step
 // ---------------------------------------------------------------------------------------------------------------------
@@ -290,12 +343,25 @@ struct PpoStepArgs {
     float one_minus_b1, b2, one_minus_b2, neg_step_size, bc2_sqrt, eps;
 };
 
-static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArgs a) {
-    __shared__ PpoLds L;
+// what differs between the learners of a population; everything else of PpoStepArgs is shared
+struct PpoLearner {
+    float *params, *exp_avg, *exp_avg_sq;
+    const float* table;
+    const int* idx;
+    float *part, *lpart;
+    unsigned int* ticket;
+    float* stats_out;
+    int table_rows;
+    float neg_step_size, bc2_sqrt;
+};
+
+// the body of ppo_step_kernel / ppo_pop_step_kernel: tile `tile` of learner `l`'s minibatch.  The shared fields are read from
+// `a`, the per-learner ones from `l` only.
+__device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, const PpoLearner& l, int tile) {
     const PpoNet& n = a.n;
-    const int tid = (int)threadIdx.x, tile = (int)blockIdx.x, row0 = tile * PPO_TB;
+    const int tid = (int)threadIdx.x, row0 = tile * PPO_TB;
     const int valid = min(PPO_TB, a.M - row0);
-    const float* p = a.params;
+    const float* p = l.params;
     const int ao = n.D, lo = n.D + n.A, adv_col = lo + 1, ro = lo + 2, vo = ro + n.R;
 
     // ---- gather (mo_ppo.py:509-511): table row idx[b] -> observation, action, old log-prob, advantage, returns, old values
@@ -303,8 +369,8 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
         const int r = o / n.D, d = o - r * n.D;
         float v = 0.0f;
         if (r < valid) {
-            const int row = min(max(a.idx[row0 + r], 0), a.table_rows - 1);
-            v = a.table[(size_t)row * a.row_w + d];
+            const int row = min(max(l.idx[row0 + r], 0), l.table_rows - 1);
+            v = l.table[(size_t)row * a.row_w + d];
         }
         L.x[o] = v;
     }
@@ -312,8 +378,8 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
         const int r = o / n.A, k = o - r * n.A;
         float v = 0.0f;
         if (r < valid) {
-            const int row = min(max(a.idx[row0 + r], 0), a.table_rows - 1);
-            v = a.table[(size_t)row * a.row_w + ao + k];
+            const int row = min(max(l.idx[row0 + r], 0), l.table_rows - 1);
+            v = l.table[(size_t)row * a.row_w + ao + k];
         }
         L.act[o] = v;
     }
@@ -321,9 +387,9 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
         const int r = o / n.R, k = o - r * n.R;
         float ret = 0.0f, ov = 0.0f;
         if (r < valid) {
-            const int row = min(max(a.idx[row0 + r], 0), a.table_rows - 1);
-            ret = a.table[(size_t)row * a.row_w + ro + k];
-            ov = a.table[(size_t)row * a.row_w + vo + k];
+            const int row = min(max(l.idx[row0 + r], 0), l.table_rows - 1);
+            ret = l.table[(size_t)row * a.row_w + ro + k];
+            ov = l.table[(size_t)row * a.row_w + vo + k];
         }
         L.ret[o] = ret;
         L.oldv[o] = ov;
@@ -331,9 +397,9 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
     if (tid < PPO_TB) {
         float lp = 0.0f, adv = 0.0f;
         if (tid < valid) {
-            const int row = min(max(a.idx[row0 + tid], 0), a.table_rows - 1);
-            lp = a.table[(size_t)row * a.row_w + lo];
-            adv = a.table[(size_t)row * a.row_w + adv_col];
+            const int row = min(max(l.idx[row0 + tid], 0), l.table_rows - 1);
+            lp = l.table[(size_t)row * a.row_w + lo];
+            adv = l.table[(size_t)row * a.row_w + adv_col];
         }
         L.row[tid * 4] = lp;
         L.row[tid * 4 + 1] = adv;
@@ -344,14 +410,14 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
     if (a.norm_adv) {
         float s = 0.0f;
         for (int b = tid; b < a.M; b += PPO_THREADS) {
-            const int row = min(max(a.idx[b], 0), a.table_rows - 1);
-            s = __fadd_rn(s, a.table[(size_t)row * a.row_w + adv_col]);
+            const int row = min(max(l.idx[b], 0), l.table_rows - 1);
+            s = __fadd_rn(s, l.table[(size_t)row * a.row_w + adv_col]);
         }
         const float mean = __fdiv_rn(ppo_tree_sum(L.red, s), a.fM);
         float q = 0.0f;
         for (int b = tid; b < a.M; b += PPO_THREADS) {
-            const int row = min(max(a.idx[b], 0), a.table_rows - 1);
-            const float dlt = __fsub_rn(a.table[(size_t)row * a.row_w + adv_col], mean);
+            const int row = min(max(l.idx[b], 0), l.table_rows - 1);
+            const float dlt = __fsub_rn(l.table[(size_t)row * a.row_w + adv_col], mean);
             q = fmaf(dlt, dlt, q);
         }
         const float var = __fmul_rn(ppo_tree_sum(L.red, q), a.inv_Mm1);
@@ -362,7 +428,7 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
     }
     __syncthreads();
 
-    float* part = a.part + (size_t)tile * n.P;
+    float* part = l.part + (size_t)tile * n.P;
 
     // ---- critic: forward, value loss (mo_ppo.py:535-547) and its gradient, backward
     ppo_mlp_forward(L, n, n.c, p, n.R);
@@ -448,7 +514,7 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
     if (tid < PPO_NPART) {
         float s = 0.0f;
         for (int r = 0; r < PPO_TB; ++r) s = __fadd_rn(s, L.rs[r * PPO_NPART + tid]);
-        a.lpart[tile * PPO_NPART + tid] = s;
+        l.lpart[tile * PPO_NPART + tid] = s;
     }
     ppo_mlp_backward(L, n, n.a, p, part, n.A);
 
@@ -456,7 +522,7 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
     __threadfence();
     __syncthreads();
     if (tid == 0) {
-        const unsigned int prev = atomicAdd(a.ticket, 1u);
+        const unsigned int prev = atomicAdd(l.ticket, 1u);
         L.last = (prev + 1u == (unsigned int)a.ntiles) ? 1 : 0;
     }
     __syncthreads();
@@ -464,19 +530,19 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
     __threadfence();
 
     // the gradient: partials summed in tile order (four loads in flight, added in order), kept in tile 0's slot
-    float* grad = a.part;
+    float* grad = l.part;
     for (int t = 0; t < n.ntensors; ++t) {
         {
             float sq = 0.0f;
             for (int q = n.tstart[t] + tid; q < n.tstart[t + 1]; q += PPO_THREADS) {
-                float g = a.part[q];
+                float g = l.part[q];
                 int tl = 1;
                 for (; tl + 4 <= a.ntiles; tl += 4) {
-                    const float g0 = a.part[(size_t)tl * n.P + q], g1 = a.part[(size_t)(tl + 1) * n.P + q];
-                    const float g2 = a.part[(size_t)(tl + 2) * n.P + q], g3 = a.part[(size_t)(tl + 3) * n.P + q];
+                    const float g0 = l.part[(size_t)tl * n.P + q], g1 = l.part[(size_t)(tl + 1) * n.P + q];
+                    const float g2 = l.part[(size_t)(tl + 2) * n.P + q], g3 = l.part[(size_t)(tl + 3) * n.P + q];
                     g = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(g, g0), g1), g2), g3);
                 }
-                for (; tl < a.ntiles; ++tl) g = __fadd_rn(g, a.part[(size_t)tl * n.P + q]);
+                for (; tl < a.ntiles; ++tl) g = __fadd_rn(g, l.part[(size_t)tl * n.P + q]);
                 if (t == 0) g = __fsub_rn(g, a.ent_coef);      // d(-ent_coef * entropy) / d logstd_k
                 grad[q] = g;
                 sq = fmaf(g, g, sq);
@@ -498,36 +564,57 @@ static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArg
         const float total = __fsqrt_rn(s);
         L.stat[2] = fminf(__fdiv_rn(a.max_grad_norm, __fadd_rn(total, 1e-6f)), 1.0f);
         L.stat[3] = total;
-        *a.ticket = 0u;                                        // re-armed for the next launch on the stream
+        *l.ticket = 0u;                                        // re-armed for the next launch on the stream
         float ls[PPO_NPART];
         for (int i = 0; i < PPO_NPART; ++i) ls[i] = 0.0f;
         for (int t = 0; t < a.ntiles; ++t)
-            for (int i = 0; i < PPO_NPART; ++i) ls[i] = __fadd_rn(ls[i], a.lpart[t * PPO_NPART + i]);
+            for (int i = 0; i < PPO_NPART; ++i) ls[i] = __fadd_rn(ls[i], l.lpart[t * PPO_NPART + i]);
         float ent = 0.0f;                                      // Normal.entropy(): 0.5 + 0.5 log(2 pi) + log(scale), the same in every row
         for (int k = 0; k < n.A; ++k) ent = __fadd_rn(ent, __fadd_rn(__fadd_rn(0.5f, PPO_HALF_LOG_2PI), logf(expf(p[n.oLs + k]))));
         const float pg = __fdiv_rn(ls[0], a.fM), v = __fmul_rn(0.5f, __fdiv_rn(ls[1], a.fMR));
-        a.stats_out[0] = __fadd_rn(__fsub_rn(pg, __fmul_rn(a.ent_coef, ent)), __fmul_rn(v, a.vf_coef));
-        a.stats_out[1] = pg;
-        a.stats_out[2] = v;
-        a.stats_out[3] = ent;
-        a.stats_out[4] = __fdiv_rn(ls[2], a.fM);
-        a.stats_out[5] = __fdiv_rn(ls[3], a.fM);
-        a.stats_out[6] = __fdiv_rn(ls[4], a.fM);
-        a.stats_out[7] = total;
+        l.stats_out[0] = __fadd_rn(__fsub_rn(pg, __fmul_rn(a.ent_coef, ent)), __fmul_rn(v, a.vf_coef));
+        l.stats_out[1] = pg;
+        l.stats_out[2] = v;
+        l.stats_out[3] = ent;
+        l.stats_out[4] = __fdiv_rn(ls[2], a.fM);
+        l.stats_out[5] = __fdiv_rn(ls[3], a.fM);
+        l.stats_out[6] = __fdiv_rn(ls[4], a.fM);
+        l.stats_out[7] = total;
     }
     __syncthreads();
     const float scale = L.stat[2];
     // torch _single_tensor_adam with eps 1e-5 (mo_ppo.py:331, 554): lerp_, mul_ + addcmul_, addcdiv_
     for (int q = tid; q < n.P; q += PPO_THREADS) {
         const float g = __fmul_rn(grad[q], scale);
-        float m = a.exp_avg[q], v = a.exp_avg_sq[q];
+        float m = l.exp_avg[q], v = l.exp_avg_sq[q];
         m = fmaf(a.one_minus_b1, __fsub_rn(g, m), m);
         v = __fadd_rn(__fmul_rn(v, a.b2), __fmul_rn(__fmul_rn(a.one_minus_b2, g), g));
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), a.bc2_sqrt), a.eps);
-        a.params[q] = __fadd_rn(a.params[q], __fmul_rn(a.neg_step_size, __fdiv_rn(m, denom)));
-        a.exp_avg[q] = m;
-        a.exp_avg_sq[q] = v;
+        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), l.bc2_sqrt), a.eps);
+        l.params[q] = __fadd_rn(l.params[q], __fmul_rn(l.neg_step_size, __fdiv_rn(m, denom)));
+        l.exp_avg[q] = m;
+        l.exp_avg_sq[q] = v;
     }
+}
+
+
+static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArgs a) {
+    __shared__ PpoLds L;
+    const PpoLearner l{a.params, a.exp_avg, a.exp_avg_sq, a.table, a.idx, a.part, a.lpart, a.ticket, a.stats_out, a.table_rows,
+                       a.neg_step_size, a.bc2_sqrt};
+    ppo_step_tile(L, a, l, (int)blockIdx.x);
+}
+
+// blockIdx.y is the learner: its own parameters, moments, table, idx, partials, ticket, statistics row and Adam scalars.  The
+// last workgroup to arrive FOR THAT LEARNER (its ticket counts to ntiles) owns that learner's step; nothing crosses learners.
+struct PpoPopStepArgs {
+    PpoStepArgs s;                      // the shared fields; its per-learner fields are not read
+    PpoLearner l[PPO_POP_CHUNK];
+};
+static_assert(sizeof(PpoPopStepArgs) <= 4096 && sizeof(PpoPopFwdArgs) <= 4096 && sizeof(PpoPopGaeArgs) <= 4096,
+              "population records travel in the kernel argument");
+static __global__ __launch_bounds__(PPO_THREADS) void ppo_pop_step_kernel(PpoPopStepArgs a) {
+    __shared__ PpoLds L;
+    ppo_step_tile(L, a.s, a.l[blockIdx.y], (int)blockIdx.x);
 }
 
 }  // namespace morl

@@ -272,6 +272,11 @@ _SIGNATURES = {
     "morl_ppo_update_n": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int] + [C.c_double] * 4 +
                           [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "morl_ppo_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
+    # the population entries: every c_void_p but the last is a host array of P handles / device pointers / scalars
+    "morl_ppo_update_n_pop": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] +
+                              [C.c_double] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "morl_ppo_forward_pop": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "morl_ppo_gae_pop": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 3),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

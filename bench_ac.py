@@ -2,7 +2,7 @@
 continuous) on one MI355X.  bench.py stays the north-star (Envelope) line the driver runs; this script measures the
 widened rows with the same conventions:
 
-    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn|ppo [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn|ppo|nlppo [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench_ac.py --workload morld --gpus N --pop 64      # the population's learners are independent units: pop / N per
                                                                 # GPU, no data-path collective ("replicas only", weak scaling)
@@ -39,6 +39,7 @@ SHAPES = {  # obs dim, action dim, objectives of the environments BASELINE.json 
     "pcn": dict(D=9, Ad=4, R=2, env="treasure-line (discrete head) / mo-hopper-v4 shapes 11-3-3 (continuous head)"),
     "ppo": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
     "pgmorl": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
+    "nlppo": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (NL-MO-PPO, discrete: 6 actions)"),
 }
 ARCH = [256, 256]
 B = 128
@@ -566,6 +567,136 @@ def bench_ppo(a):
     print(json.dumps(out), file=RESULT_OUT, flush=True)
 
 
+def bench_nlppo(a):
+    """NL-MO-PPO (single_policy/ser/nl_mo_ppo.py): one ``NLMOPPO.update()`` at the class defaults -- 4 envs x 128 steps = 512 rows,
+    4 epochs x 4 minibatches of 128 rows = 16 optimiser steps, net [64, 64], mo-minecart shapes (obs 7, 6 actions, 3 objectives,
+    pref_dim 3) -- as ONE ``morl_nlppo_update_n`` call, and the GAE scan over 128 x 4; next to it the same steps as eager torch ops
+    on the same GPU (tests/nlppo_oracle.py moved to the device, with the reference's host read of ``clipfrac`` per minibatch).  The
+    loss weights are fixed: ``_compute_loss_weights`` is one forward launch and a host gradient in both legs.  The two legs
+    alternate, ``--steps`` updates per timed window, five windows each; the figure is the median window."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ctypes as C
+
+    import nlppo_oracle as no
+    from morl_baselines_amd.native import load_library
+
+    lib, dev = load_library(), th.device("cuda", 0)
+    T, E, D, A, R, Pd, hidden = 128, 4, 7, 6, 3, 3, [64, 64]
+    epochs, n_mb, lr, gamma, lam = 4, 4, 2.5e-4, 0.99, 0.95
+    rows, M, n_steps = T * E, T * E // n_mb, epochs * n_mb
+    loops = max(1, a.steps)
+    th.manual_seed(0)
+    net = no.Agent(D, A, R, Pd, hidden)
+    g = th.Generator().manual_seed(1)
+    old = copy.deepcopy(net)
+    with th.no_grad():
+        for p in old.parameters():
+            p.add_(0.05 * th.randn(p.shape, generator=g))
+        obs, acc, pref = th.randn(rows, D, generator=g), 0.5 * th.randn(rows, R, generator=g), th.rand(R, generator=g)
+        actions = th.multinomial(th.softmax(old.logits(obs, acc, pref), -1), 1, generator=g).reshape(-1)
+        _, logprobs, _, values = old.get_action_and_value(obs, acc, action=actions, pref=pref)
+    rewards = th.randn(rows, R, generator=g)
+    dones = (th.rand(rows, generator=g) < 0.01).float()
+    next_value, next_done = th.randn(E, R, generator=g), th.zeros(E)
+    weights = th.tensor([1.05, 0.035, -0.2])
+    rng = np.random.default_rng(0)
+    b_inds, idx = np.arange(rows), []
+    for _ in range(epochs):
+        rng.shuffle(b_inds)
+        idx += [b_inds[s:s + M].copy() for s in range(0, rows, M)]
+    idx = np.stack(idx).astype(np.int32)
+    to = lambda t: t.to(dev).contiguous()  # noqa: E731
+    obs_d, acc_d, lp_d, rew_d, done_d, val_d, pref_d = (to(t) for t in (obs, acc, logprobs, rewards, dones, values, pref))
+    act_d, act_l = to(actions.int()), to(actions)
+    nv_d, nd_d, w_d, idx_d = to(next_value), to(next_done), to(weights), th.tensor(idx).to(dev)
+    idx_l = idx_d.long()
+
+    h = C.c_void_p()
+    lib.check(lib.lib.morl_nlppo_create(C.byref(h), D, A, R, Pd, 2, hidden[0], hidden[1], M))
+    stream = lib.stream_of(obs_d)
+    lib.check(lib.lib.morl_nlppo_set_rollout(h, obs_d.data_ptr(), acc_d.data_ptr(), act_d.data_ptr(), lp_d.data_ptr(), rew_d.data_ptr(),
+                                             done_d.data_ptr(), val_d.data_ptr(), pref_d.data_ptr(), T, E, stream))
+    ret_d, adv_d = th.zeros(rows, R, device=dev), th.zeros(rows, R, device=dev)
+
+    def fused_gae():
+        lib.check(lib.lib.morl_nlppo_gae(h, nv_d.data_ptr(), nd_d.data_ptr(), gamma, lam, ret_d.data_ptr(), adv_d.data_ptr(), stream))
+
+    def eager_gae():
+        return no.compute_advantages(rew_d.view(T, E, R), done_d.view(T, E), val_d.view(T, E, R), nv_d, nd_d, gamma, lam)
+
+    fused_gae()
+    e_adv, e_ret = eager_gae()
+    th.cuda.synchronize()
+    gae_diff = float((adv_d - e_adv.reshape(rows, R)).abs().max() / e_adv.abs().max())
+
+    flat0 = th.cat([p.detach().reshape(-1) for p in net.parameters()]).to(dev)
+    state = dict(p=flat0.clone(), m=th.zeros_like(flat0), v=th.zeros_like(flat0), steps=0)
+    stats_d = th.zeros(n_steps, 8, device=dev)
+
+    def fused_update():
+        lib.check(lib.lib.morl_nlppo_update_n(h, state["p"].data_ptr(), state["m"].data_ptr(), state["v"].data_ptr(), n_steps,
+                                              idx_d.data_ptr(), M, w_d.data_ptr(), lr, state["steps"], 0.2, 0.01, 0.5, 0.5, 1, 1,
+                                              stats_d.data_ptr(), stream))
+        state["steps"] += n_steps
+
+    e_net = copy.deepcopy(net).to(dev)
+    e_net.aug = lambda x, ar, p: th.cat([x, ar, p], dim=-1)      # (the rows, already on the device)
+    opt = th.optim.Adam(e_net.parameters(), lr=lr, eps=1e-5)
+    cfg = no.Cfg()
+    batch = (obs_d, acc_d, act_l, lp_d, e_adv.reshape(rows, R), e_ret.reshape(rows, R), val_d, pref_d)
+    eager_losses = []
+
+    def eager_update():
+        eager_losses.clear()
+        clipfracs = []
+        for k in range(n_steps):
+            s, _ = no.minibatch_step(e_net, opt, cfg, batch, w_d, idx_l[k])
+            clipfracs.append(s[6].item())            # the reference's host read per minibatch (nl_mo_ppo.py:362)
+            eager_losses.append(s[0])
+
+    # same inputs, same start: the first update of each leg must agree before anything is timed
+    fused_update()
+    eager_update()
+    th.cuda.synchronize()
+    e_loss = th.stack(eager_losses)
+    first = slice(0, n_mb)                           # the first epoch: later steps start from parameters that have drifted apart
+    loss_diff = float((stats_d[first, 0] - e_loss[first]).abs().max() / e_loss[first].abs().max())
+    for _ in range(max(1, a.warmup // 10)):
+        fused_update()
+        eager_update()
+    th.cuda.synchronize()
+    t = {"fused": [], "eager": [], "fused_gae": [], "eager_gae": []}
+    for _ in range(5):
+        for name, fn, reps, per in (("fused", fused_update, loops, n_steps), ("eager", eager_update, max(1, loops // 10), n_steps),
+                                    ("fused_gae", fused_gae, loops, 1), ("eager_gae", eager_gae, max(1, loops // 10), 1)):
+            th.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            th.cuda.synchronize()
+            t[name].append((time.perf_counter() - t0) * 1e3 / (reps * per))
+    lib.lib.morl_nlppo_destroy(h)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    out = {"metric": "NL-MO-PPO optimiser steps/sec (one-entry 16-step update())", "value": 1e3 / med["fused"], "unit": "steps/s",
+           "n_gpus": 1, "steps": loops, "warmup": a.warmup, "ms_per_step": med["fused"], "higher_is_better": True, "vs_baseline": None,
+           "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "NLMOPPO.update() at the class defaults: 512-row rollout (4 envs x 128 steps), 4 epochs x 4 "
+                                  "minibatches of 128, net [64, 64], shapes of mo-minecart (obs 7, 6 actions, 3 objectives, pref_dim 3); "
+                                  "one morl_nlppo_update_n call per update(); comparison: the same steps as eager torch ops on the "
+                                  "same GPU"},
+           "shape": dict(obs_dim=D, n_actions=A, reward_dim=R, pref_dim=Pd, hidden=hidden, rollout_rows=rows, minibatch=M,
+                         steps_per_update=n_steps),
+           "fused_us_per_step": med["fused"] * 1e3, "eager_torch_us_per_step": med["eager"] * 1e3,
+           "eager_over_fused": med["eager"] / med["fused"], "fused_windows_ms": t["fused"], "eager_windows_ms": t["eager"],
+           "first_epoch_loss_rel_diff": loss_diff,
+           "gae": {"fused_ms": med["fused_gae"], "eager_torch_ms": med["eager_gae"], "eager_over_fused": med["eager_gae"] / med["fused_gae"],
+                   "advantage_rel_diff": gae_diff, "fused_windows_ms": t["fused_gae"], "eager_windows_ms": t["eager_gae"]},
+           "loops_per_window": {"fused": loops, "eager": max(1, loops // 10)},
+           "roofline": {"bound": "latency", "kernel": "nlppo_step_kernel", "achieved": None, "peak": None, "unit": None, "frac": None,
+                        "traffic": None, "note": "8 tiles of 16 rows, ~5 MFLOP and < 1 MB per step: launch- and dependency-latency-bound"}}
+    print(json.dumps(out), file=RESULT_OUT, flush=True)
+
+
 def bench_pgmorl(a):
     """PGMORL's population (multi_policy/pgmorl/pgmorl.py, ``pop_size`` MOPPO learners) at the ``ppo`` row's shapes: every learner
     has its own parameters, rollout and shuffles.  Three pairs, each timed in the same process in interleaved windows (five per leg,
@@ -828,6 +959,8 @@ def main():
         return bench_pcn(a)
     if a.workload == "ppo":
         return bench_ppo(a)
+    if a.workload == "nlppo":
+        return bench_nlppo(a)
     if a.workload == "pgmorl":
         return bench_pgmorl(a)
     from morl_baselines_amd.ac_engine import ALGO_CAPQL, ALGO_MOSAC, ALGO_TD3, ACEngine

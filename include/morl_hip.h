@@ -909,6 +909,58 @@ int morl_ppo_gae_pop(int P, morl_ppo_ctx* const* ctxs, const float* const* next_
                      const float* const* weights, double gamma, double gae_lambda, int use_gae, float* const* returns_out,
                      float* const* advantages_out, void* stream);
 
+/* ================================================================================================
+ * Non-linear multi-objective PPO (single_policy/ser/nl_mo_ppo.py), the learner IPRO calls for every Pareto-oracle query
+ *   Agent (:26-108):        input = obs | accrued discounted reward [R] | preference [pref_dim] (zeros when there is none);
+ *                           critic input -> hidden (Tanh) -> [R];  actor input -> hidden (Tanh) -> logits [A], Categorical
+ *   update() (:346-393):    per minibatch: gather, forward, per-objective advantage normalisation, per-objective clipped
+ *                           surrogate combined by loss_weights (du/dv at v(s0), any sign), (clipped) value loss, the entropy of
+ *                           the categorical policy (back-propagated through the actor), backward, clip_grad_norm_,
+ *                           Adam(eps = 1e-5) -- one launch per minibatch step
+ *   _compute_advantages_and_returns (:290-308): GAE that keeps the advantage vector [R]
+ * Parameters are one flat fp32 vector in the order of Agent.parameters():
+ *   critic.0.weight [H0][D_in], critic.0.bias, critic.2.*, (critic.4.*), actor.0.*, actor.2.*, (actor.4.*) -- the .4 entries exist
+ *   with two hidden layers only; D_in = obs_dim + reward_dim + pref_dim.
+ * Limits (MORL_ERR_ARG otherwise): obs_dim >= 1, D_in <= 128, n_actions 2..32, reward_dim 1..8, pref_dim 0 or reward_dim, one or
+ * two hidden layers of width 32 | 64 | 96 | 128 each.
+ * The entries take scalars and pointers only; every pointer is device memory; nothing synchronises the host.  A refused call
+ * launches nothing and leaves the context usable.
+ * ================================================================================================ */
+typedef struct morl_nlppo_ctx morl_nlppo_ctx;
+
+/* -1 (and morl_last_error) for a shape outside the limits; hidden1 is ignored when n_hidden == 1 */
+int64_t morl_nlppo_param_count(int obs_dim, int n_actions, int reward_dim, int pref_dim, int n_hidden, int hidden0, int hidden1);
+/* max_minibatch: largest M of morl_nlppo_update_n */
+int morl_nlppo_create(morl_nlppo_ctx** out, int obs_dim, int n_actions, int reward_dim, int pref_dim, int n_hidden, int hidden0,
+                      int hidden1, int max_minibatch);
+int morl_nlppo_destroy(morl_nlppo_ctx* ctx);
+/* Replace the context's rollout with T steps of E envs, row t * E + e:  obs [T*E][obs_dim], acc_rewards [T*E][R], actions [T*E]
+ * (int32 indices; one outside [0, n_actions) is clamped when a step gathers it), logprobs [T*E], rewards [T*E][R], dones [T*E]
+ * (0 / 1 as floats: the done flag seen BEFORE step t), values [T*E][R], pref [pref_dim] or NULL (zeros; ignored when pref_dim
+ * is 0).  The context keeps its own table, one row per (step, env):
+ *   input [D_in] | action | old log-prob | advantages [R] | returns [R] | old values [R];  morl_nlppo_gae fills the middle columns. */
+int morl_nlppo_set_rollout(morl_nlppo_ctx* ctx, const float* obs, const float* acc_rewards, const int32_t* actions,
+                           const float* logprobs, const float* rewards, const float* dones, const float* values, const float* pref,
+                           int T, int E, void* stream);
+/* The reverse GAE scan over the rollout: next_value [E][R], next_done [E].  gamma * gae_lambda is formed in double.
+ * returns_out [T*E][R] / advantages_out [T*E][R]: copies, or NULL. */
+int morl_nlppo_gae(morl_nlppo_ctx* ctx, const float* next_value, const float* next_done, double gamma, double gae_lambda,
+                   float* returns_out, float* advantages_out, void* stream);
+/* n minibatch steps, one launch each, enqueued back to back.  idx [n][M] int32 rows of the rollout (step k trains on idx[k]);
+ * loss_weights [R] on the device; Adam with betas 0.9 / 0.999 and eps 1e-5, adam_steps_done = steps taken before this call.
+ * norm_adv (one mean / unbiased std per objective) needs M >= 2.
+ * stats_out [n][8]: loss, pg_loss, v_loss, entropy (mean over the rows), old_approx_kl, approx_kl, clipfrac, grad_norm (before
+ * clipping) of each step.  Results are bit-identical run to run, and n steps in one call equal n calls of one step. */
+int morl_nlppo_update_n(morl_nlppo_ctx* ctx, float* params, float* exp_avg, float* exp_avg_sq, int n, const int32_t* idx, int M,
+                        const float* loss_weights, double lr, int adam_steps_done, double clip_coef, double ent_coef, double vf_coef,
+                        double max_grad_norm, int clip_vloss, int norm_adv, float* stats_out, void* stream);
+/* No-grad forward on obs [rows][obs_dim], acc_reward [rows][R], pref [pref_dim] or NULL (zeros): value_out [rows][R] and
+ * logp_out [rows][n_actions], the normalised log-probabilities (logits - logsumexp), computed as a step computes them: the entry
+ * of a stored action is what the next step reproduces bit for bit while the parameters are unchanged.  Sampling and the arg-max
+ * of get_greedy_action are the caller's.  value_only != 0 is get_value: the actor is skipped and logp_out may be NULL. */
+int morl_nlppo_forward(morl_nlppo_ctx* ctx, const float* params, const float* obs, const float* acc_reward, const float* pref,
+                       int rows, int value_only, float* logp_out, float* value_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

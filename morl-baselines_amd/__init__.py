@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("MOPPO", "MOPPONet"):
         from . import mo_ppo
         return getattr(mo_ppo, name)
+    if name in ("NLMOPPO", "Agent"):
+        from . import nl_mo_ppo
+        return getattr(nl_mo_ppo, name)
     if name == "PGMORL":
         from .pgmorl import PGMORL
         return PGMORL

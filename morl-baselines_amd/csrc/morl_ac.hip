@@ -2622,3 +2622,199 @@ extern "C" int morl_ppo_gae_pop(int P, morl_ppo_ctx* const* ctxs, const float* c
     for (int i = 0; i < P; ++i) ctxs[i]->have_gae = 1;
     return MORL_OK;
 }
+
+
+// =====================================================================================================================
+// Non-linear multi-objective PPO (include/morl_hip.h, "Non-linear multi-objective PPO")
+// =====================================================================================================================
+#include "nlppo_kernels.h"
+
+struct morl_nlppo_ctx {
+    PpoNet n{};                    // n.D = obs_dim + reward_dim + pref_dim
+    NlppoIn in{};
+    int max_minibatch = 0, max_tiles = 0, row_w = 0;
+    float* table = nullptr;        // [rows_cap][row_w]
+    float* rewards = nullptr;      // [rows_cap][R]
+    float* dones = nullptr;        // [rows_cap]
+    int64_t rows_cap = 0;
+    int T = 0, E = 0, have_gae = 0;
+    float* part = nullptr;         // [max_tiles][P]
+    float* lpart = nullptr;        // [max_tiles][NLPPO_NPART]
+    unsigned int* ticket = nullptr;
+};
+
+static int nlppo_fill(PpoNet& n, NlppoIn& in, int obs_dim, int A, int R, int pref_dim, int nh, int h0, int h1) {
+    if (obs_dim < 1) return fail(MORL_ERR_ARG, "NL-MO-PPO: obs_dim %d is not at least 1", obs_dim);
+    if (R < 1 || R > PPO_MAX_R) return fail(MORL_ERR_ARG, "NL-MO-PPO: reward_dim %d outside 1..%d", R, PPO_MAX_R);
+    if (pref_dim != 0 && pref_dim != R) return fail(MORL_ERR_ARG, "NL-MO-PPO: pref_dim %d is neither 0 nor reward_dim %d", pref_dim, R);
+    if ((int64_t)obs_dim + R + pref_dim > PPO_MAX_D)
+        return fail(MORL_ERR_ARG, "NL-MO-PPO: input width obs_dim %d + reward_dim %d + pref_dim %d exceeds %d", obs_dim, R, pref_dim,
+                    PPO_MAX_D);
+    if (A < 2 || A > PPO_MAX_A) return fail(MORL_ERR_ARG, "NL-MO-PPO: n_actions %d outside 2..%d", A, PPO_MAX_A);
+    if (nh < 1 || nh > 2) return fail(MORL_ERR_ARG, "NL-MO-PPO: n_hidden %d is not 1 or 2 hidden layers", nh);
+    const int hs[2] = {h0, h1};
+    for (int l = 0; l < nh; ++l)
+        if (hs[l] < 32 || hs[l] > PPO_MAX_H || hs[l] % 32 != 0)
+            return fail(MORL_ERR_ARG, "NL-MO-PPO: hidden width %d (layer %d) is not one of 32, 64, 96, 128", hs[l], l);
+    const int D = obs_dim + R + pref_dim;
+    in.obs_dim = obs_dim; in.pref_dim = pref_dim;
+    n.D = D; n.A = A; n.R = R; n.nh = nh; n.H1 = h0; n.H2 = (nh == 2) ? h1 : h0;
+    n.oLs = 0;
+    int o = 0, t = 0;
+    auto take = [&](int count) { const int at = o; n.tstart[t++] = o; o += count; return at; };
+    for (int which = 0; which < 2; ++which) {
+        PpoMlp& m = which ? n.a : n.c;
+        const int N = which ? A : R;
+        m.oW0 = take(n.H1 * D);
+        m.ob0 = take(n.H1);
+        m.oW1 = m.ob1 = 0;
+        if (nh == 2) {
+            m.oW1 = take(n.H2 * n.H1);
+            m.ob1 = take(n.H2);
+        }
+        m.oWo = take(N * n.H2);
+        m.obo = take(N);
+    }
+    n.P = o;
+    n.ntensors = t;
+    for (int i = t; i <= PPO_MAX_TENSORS; ++i) n.tstart[i] = o;
+    return MORL_OK;
+}
+
+extern "C" int64_t morl_nlppo_param_count(int obs_dim, int n_actions, int reward_dim, int pref_dim, int n_hidden, int hidden0,
+                                          int hidden1) {
+    PpoNet n{};
+    NlppoIn in{};
+    return nlppo_fill(n, in, obs_dim, n_actions, reward_dim, pref_dim, n_hidden, hidden0, hidden1) ? -1 : n.P;
+}
+
+extern "C" int morl_nlppo_destroy(morl_nlppo_ctx* c) {
+    if (!c) return MORL_OK;
+    for (void* p : {(void*)c->table, (void*)c->rewards, (void*)c->dones, (void*)c->part, (void*)c->lpart, (void*)c->ticket})
+        if (p) (void)hipFree(p);
+    delete c;
+    return MORL_OK;
+}
+
+extern "C" int morl_nlppo_create(morl_nlppo_ctx** out, int obs_dim, int n_actions, int reward_dim, int pref_dim, int n_hidden,
+                                 int hidden0, int hidden1, int max_minibatch) {
+    if (!out) return fail(MORL_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    PpoNet n{};
+    NlppoIn in{};
+    int rc = nlppo_fill(n, in, obs_dim, n_actions, reward_dim, pref_dim, n_hidden, hidden0, hidden1);
+    if (rc) return rc;
+    if (max_minibatch < 1 || max_minibatch > (1 << 20))
+        return fail(MORL_ERR_ARG, "NL-MO-PPO: max_minibatch %d outside 1..%d", max_minibatch, 1 << 20);
+    morl_nlppo_ctx* c = new (std::nothrow) morl_nlppo_ctx();
+    if (!c) return fail(MORL_ERR_ALLOC, "out of host memory");
+    c->n = n;
+    c->in = in;
+    c->max_minibatch = max_minibatch;
+    c->max_tiles = (max_minibatch + PPO_TB - 1) / PPO_TB;
+    c->row_w = n.D + 2 + 3 * reward_dim;
+    if ((rc = dmalloc((void**)&c->part, (size_t)c->max_tiles * n.P * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->lpart, (size_t)c->max_tiles * NLPPO_NPART * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->ticket, sizeof(unsigned int)))) {
+        morl_nlppo_destroy(c);
+        return rc;
+    }
+    if (hipMemset(c->ticket, 0, sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        morl_nlppo_destroy(c);
+        return fail(MORL_ERR_HIP, "NL-MO-PPO: workspace init failed");
+    }
+    *out = c;
+    return MORL_OK;
+}
+
+extern "C" int morl_nlppo_set_rollout(morl_nlppo_ctx* c, const float* obs, const float* acc_rewards, const int32_t* actions,
+                                      const float* logprobs, const float* rewards, const float* dones, const float* values,
+                                      const float* pref, int T, int E, void* stream) {
+    if (!c || !obs || !acc_rewards || !actions || !logprobs || !rewards || !dones || !values) return fail(MORL_ERR_ARG, "NULL argument");
+    if (T < 1 || E < 1 || (int64_t)T * E > (int64_t)(1 << 24))
+        return fail(MORL_ERR_ARG, "NL-MO-PPO: rollout of %d steps x %d envs (at most %d rows)", T, E, 1 << 24);
+    const int64_t rows = (int64_t)T * E;
+    const int R = c->n.R;
+    if (rows > c->rows_cap) {
+        // (hipFree waits for the work that may still read the old buffers)
+        for (float** p : {&c->table, &c->rewards, &c->dones})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        c->rows_cap = 0; c->T = c->E = 0;
+        int rc;
+        if ((rc = dmalloc((void**)&c->table, (size_t)rows * c->row_w * sizeof(float))) ||
+            (rc = dmalloc((void**)&c->rewards, (size_t)rows * R * sizeof(float))) ||
+            (rc = dmalloc((void**)&c->dones, (size_t)rows * sizeof(float))))
+            return rc;
+        c->rows_cap = rows;
+    }
+    HIP_TRY(hipMemcpyAsync(c->rewards, rewards, (size_t)rows * R * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(c->dones, dones, (size_t)rows * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    const int64_t total = rows * c->row_w;
+    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 1024);
+    hipLaunchKernelGGL(nlppo_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c->in.obs_dim, R, c->in.pref_dim, c->row_w,
+                       (int)rows, obs, acc_rewards, (const int*)actions, logprobs, values, c->in.pref_dim ? pref : nullptr, c->table);
+    LAUNCH_CHECK("nlppo_pack");
+    c->T = T; c->E = E; c->have_gae = 0;
+    return MORL_OK;
+}
+
+extern "C" int morl_nlppo_gae(morl_nlppo_ctx* c, const float* next_value, const float* next_done, double gamma, double gae_lambda,
+                              float* returns_out, float* advantages_out, void* stream) {
+    if (!c || !next_value || !next_done) return fail(MORL_ERR_ARG, "NULL argument");
+    if (c->T < 1) return fail(MORL_ERR_STATE, "NL-MO-PPO: no rollout (morl_nlppo_set_rollout)");
+    hipLaunchKernelGGL(nlppo_gae_kernel, dim3((c->E + 63) / 64), dim3(64), 0, (hipStream_t)stream, c->T, c->E, c->n.R, c->row_w,
+                       c->n.D + 2, c->table, c->rewards, c->dones, next_value, next_done, (float)gamma, (float)(gamma * gae_lambda),
+                       returns_out, advantages_out);
+    LAUNCH_CHECK("nlppo_gae");
+    c->have_gae = 1;
+    return MORL_OK;
+}
+
+extern "C" int morl_nlppo_update_n(morl_nlppo_ctx* c, float* params, float* exp_avg, float* exp_avg_sq, int n, const int32_t* idx,
+                                   int M, const float* loss_weights, double lr, int adam_steps_done, double clip_coef,
+                                   double ent_coef, double vf_coef, double max_grad_norm, int clip_vloss, int norm_adv,
+                                   float* stats_out, void* stream) {
+    if (!c || !params || !exp_avg || !exp_avg_sq || !idx || !loss_weights || !stats_out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (n < 1) return fail(MORL_ERR_ARG, "n = %d updates", n);
+    if (M < 1 || M > c->max_minibatch)
+        return fail(MORL_ERR_STATE, "NL-MO-PPO: minibatch %d outside 1..max_minibatch %d", M, c->max_minibatch);
+    if (norm_adv && M < 2) return fail(MORL_ERR_ARG, "NL-MO-PPO: norm_adv needs a minibatch of at least 2 rows (std of %d)", M);
+    if (c->T < 1) return fail(MORL_ERR_STATE, "NL-MO-PPO: no rollout (morl_nlppo_set_rollout)");
+    if (!c->have_gae) return fail(MORL_ERR_STATE, "NL-MO-PPO: the rollout has no advantages yet (morl_nlppo_gae)");
+    if (adam_steps_done < 0) return fail(MORL_ERR_ARG, "adam_steps_done %d", adam_steps_done);
+    NlppoStepArgs a{};
+    a.n = c->n;
+    a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
+    a.table = c->table; a.table_rows = c->T * c->E; a.row_w = c->row_w;
+    a.M = M; a.ntiles = (M + PPO_TB - 1) / PPO_TB;
+    a.loss_weights = loss_weights;
+    a.part = c->part; a.lpart = c->lpart; a.ticket = c->ticket;
+    a.clip_lo = (float)(1.0 - clip_coef); a.clip_hi = (float)(1.0 + clip_coef); a.clip_coef = (float)clip_coef;
+    a.ent_coef = (float)ent_coef; a.vf_coef = (float)vf_coef; a.max_grad_norm = (float)max_grad_norm;
+    a.clip_vloss = clip_vloss ? 1 : 0; a.norm_adv = norm_adv ? 1 : 0;
+    a.inv_M = (float)(1.0 / M); a.inv_MR = (float)(1.0 / ((double)M * c->n.R)); a.inv_Mm1 = M > 1 ? (float)(1.0 / (M - 1)) : 0.0f;
+    a.fM = (float)M; a.fMR = (float)((double)M * c->n.R);
+    const double b1 = 0.9, b2 = 0.999;
+    a.one_minus_b1 = (float)(1.0 - b1); a.b2 = (float)b2; a.one_minus_b2 = (float)(1.0 - b2); a.eps = 1e-5f;
+    for (int k = 0; k < n; ++k) {
+        const int step = adam_steps_done + k + 1;
+        a.neg_step_size = (float)(-(lr / (1.0 - std::pow(b1, step))));
+        a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, step));
+        a.idx = idx + (size_t)k * M;
+        a.stats_out = stats_out + (size_t)k * PPO_NSTATS;
+        hipLaunchKernelGGL(nlppo_step_kernel, dim3(a.ntiles), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
+        LAUNCH_CHECK("nlppo_step");
+    }
+    return MORL_OK;
+}
+
+extern "C" int morl_nlppo_forward(morl_nlppo_ctx* c, const float* params, const float* obs, const float* acc_reward,
+                                  const float* pref, int rows, int value_only, float* logp_out, float* value_out, void* stream) {
+    if (!c || !params || !obs || !acc_reward || !value_out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (!value_only && !logp_out) return fail(MORL_ERR_ARG, "NL-MO-PPO: logp_out is NULL");
+    if (rows < 1) return fail(MORL_ERR_ARG, "NL-MO-PPO: rows = %d", rows);
+    hipLaunchKernelGGL(nlppo_forward_kernel, dim3((rows + PPO_TB - 1) / PPO_TB), dim3(PPO_THREADS), 0, (hipStream_t)stream, c->n, c->in,
+                       params, obs, acc_reward, c->in.pref_dim ? pref : nullptr, rows, value_only ? 1 : 0, logp_out, value_out);
+    LAUNCH_CHECK("nlppo_forward");
+    return MORL_OK;
+}

@@ -277,6 +277,14 @@ _SIGNATURES = {
                               [C.c_double] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "morl_ppo_forward_pop": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
     "morl_ppo_gae_pop": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 3),
+    "morl_nlppo_param_count": (C.c_int64, [C.c_int] * 7),
+    "morl_nlppo_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 8),
+    "morl_nlppo_destroy": (C.c_int, [C.c_void_p]),
+    "morl_nlppo_set_rollout": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p]),
+    "morl_nlppo_gae": (C.c_int, [C.c_void_p] * 3 + [C.c_double, C.c_double] + [C.c_void_p] * 3),
+    "morl_nlppo_update_n": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int] +
+                            [C.c_double] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "morl_nlppo_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

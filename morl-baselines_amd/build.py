@@ -17,8 +17,11 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmorl_hip.so")
 SOURCES = ["morl_hip.hip", "morl_ac.hip", "morl_comm.hip"]
-HEADERS = ["morl_device.h", "morl_host.h", "gemm_f32.h", "envelope_kernels.h", "mlp_chain.h", "mlp_chain2.h", "mlp_chain16.h", "mlp_chain4.h", "mlp_chain_bf.h", "mlp_chain_bfn.h", "mlp_chain_bf2.h", "mlp_chain_bf_roll.h", "dw_tiles.h", "dw_bf.h", "optim_kernels.h",
-           "replay_kernels.h", "pareto_kernels.h", "metrics_kernels.h", "ac_kernels.h", "gemm_wave.h", "gpi_kernels.h", "ens_kernels.h", "pcn_kernels.h", "ppo_kernels.h"]
+
+
+def _headers() -> list:
+    """Every header of csrc/: an edit to any of them makes build_library() rebuild (no hand-kept list to forget one in)."""
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 
 
 def _hipcc() -> str:
@@ -32,7 +35,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(ROOT, "include", "morl_hip.h")]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + _headers()] + [os.path.join(ROOT, "include", "morl_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -60,7 +63,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         base.append("-DC4_PROF")
     obj_dir = os.path.join(LIB_DIR, "obj")
     os.makedirs(obj_dir, exist_ok=True)
-    deps = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", "morl_hip.h")]
+    deps = [os.path.join(CSRC, h) for h in _headers()] + [os.path.join(ROOT, "include", "morl_hip.h")]
     jobs = []
     for src in SOURCES:                     # translation units compile concurrently, unchanged ones are kept
         obj = os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")

@@ -2299,7 +2299,9 @@ extern "C" int morl_pcn_forward(morl_pcn_ctx* c, const float* params, const floa
 
 static_assert(PPO_MAX_R == MORL_MAX_OBJ, "MO-PPO reward_dim limit is MORL_MAX_OBJ");
 
-struct morl_ppo_ctx {
+// What an MO-PPO and an NL-MO-PPO context both hold: the network, the rollout on the device and the step's workspace.  The two
+// context types derive from it; the functions below take the algorithm's names for their messages.
+struct PpoWork {
     PpoNet n{};
     int max_minibatch = 0, max_tiles = 0, row_w = 0;
     float* table = nullptr;        // [rows_cap][row_w]
@@ -2308,23 +2310,28 @@ struct morl_ppo_ctx {
     int64_t rows_cap = 0;
     int T = 0, E = 0, have_gae = 0;
     float* part = nullptr;         // [max_tiles][P]
-    float* lpart = nullptr;        // [max_tiles][PPO_NPART]
+    float* lpart = nullptr;        // [max_tiles][PPO_NPART or NLPPO_NPART]
     unsigned int* ticket = nullptr;
 };
+struct PpoNames {
+    const char *algo, *abi;        // "MO-PPO", "morl_ppo"
+};
+static const PpoNames PPO_NAMES{"MO-PPO", "morl_ppo"}, NLPPO_NAMES{"NL-MO-PPO", "morl_nlppo"};
 
-static int ppo_fill(PpoNet& n, int D, int A, int R, int nh, int h0, int h1) {
-    if (D < 1 || D > PPO_MAX_D) return fail(MORL_ERR_ARG, "MO-PPO: obs_dim %d outside 1..%d", D, PPO_MAX_D);
-    if (A < 1 || A > PPO_MAX_A) return fail(MORL_ERR_ARG, "MO-PPO: action_dim %d outside 1..%d", A, PPO_MAX_A);
-    if (R < 1 || R > PPO_MAX_R) return fail(MORL_ERR_ARG, "MO-PPO: reward_dim %d outside 1..%d", R, PPO_MAX_R);
-    if (nh < 1 || nh > 2) return fail(MORL_ERR_ARG, "MO-PPO: n_hidden %d is not 1 or 2 hidden layers", nh);
+struct morl_ppo_ctx : PpoWork {};
+
+// The flat parameter vector of the two MLPs in the order of parameters(): actor_logstd [A] first if the learner has one
+// (MO-PPO), then critic.*, then the actor.  D, A and R are checked by the caller.
+static int ppo_layout(PpoNet& n, const char* algo, bool logstd, int D, int A, int R, int nh, int h0, int h1) {
+    if (nh < 1 || nh > 2) return fail(MORL_ERR_ARG, "%s: n_hidden %d is not 1 or 2 hidden layers", algo, nh);
     const int hs[2] = {h0, h1};
     for (int l = 0; l < nh; ++l)
         if (hs[l] < 32 || hs[l] > PPO_MAX_H || hs[l] % 32 != 0)
-            return fail(MORL_ERR_ARG, "MO-PPO: hidden width %d (layer %d) is not one of 32, 64, 96, 128", hs[l], l);
+            return fail(MORL_ERR_ARG, "%s: hidden width %d (layer %d) is not one of 32, 64, 96, 128", algo, hs[l], l);
     n.D = D; n.A = A; n.R = R; n.nh = nh; n.H1 = h0; n.H2 = (nh == 2) ? h1 : h0;
     int o = 0, t = 0;
     auto take = [&](int count) { const int at = o; n.tstart[t++] = o; o += count; return at; };
-    n.oLs = take(A);
+    n.oLs = logstd ? take(A) : 0;
     for (int which = 0; which < 2; ++which) {
         PpoMlp& m = which ? n.a : n.c;
         const int N = which ? A : R;
@@ -2344,15 +2351,124 @@ static int ppo_fill(PpoNet& n, int D, int A, int R, int nh, int h0, int h1) {
     return MORL_OK;
 }
 
+static int ppo_fill(PpoNet& n, int D, int A, int R, int nh, int h0, int h1) {
+    if (D < 1 || D > PPO_MAX_D) return fail(MORL_ERR_ARG, "MO-PPO: obs_dim %d outside 1..%d", D, PPO_MAX_D);
+    if (A < 1 || A > PPO_MAX_A) return fail(MORL_ERR_ARG, "MO-PPO: action_dim %d outside 1..%d", A, PPO_MAX_A);
+    if (R < 1 || R > PPO_MAX_R) return fail(MORL_ERR_ARG, "MO-PPO: reward_dim %d outside 1..%d", R, PPO_MAX_R);
+    return ppo_layout(n, "MO-PPO", true, D, A, R, nh, h0, h1);
+}
+
 extern "C" int64_t morl_ppo_param_count(int obs_dim, int action_dim, int reward_dim, int n_hidden, int hidden0, int hidden1) {
     PpoNet n{};
     return ppo_fill(n, obs_dim, action_dim, reward_dim, n_hidden, hidden0, hidden1) ? -1 : n.P;
 }
 
+static void ppo_work_free(PpoWork* w) {
+    for (void* p : {(void*)w->table, (void*)w->rewards, (void*)w->dones, (void*)w->part, (void*)w->lpart, (void*)w->ticket})
+        if (p) (void)hipFree(p);
+}
+
+// a new context of either type with its workspace: gradient partials, lpart_w loss partial sums per tile, the zeroed ticket
+template <class Ctx>
+static int ppo_work_create(Ctx** out, const PpoNames& nm, const PpoNet& n, int max_minibatch, int row_w, int lpart_w) {
+    if (max_minibatch < 1 || max_minibatch > (1 << 20))
+        return fail(MORL_ERR_ARG, "%s: max_minibatch %d outside 1..%d", nm.algo, max_minibatch, 1 << 20);
+    Ctx* c = new (std::nothrow) Ctx();
+    if (!c) return fail(MORL_ERR_ALLOC, "out of host memory");
+    c->n = n;
+    c->max_minibatch = max_minibatch;
+    c->max_tiles = (max_minibatch + PPO_TB - 1) / PPO_TB;
+    c->row_w = row_w;
+    int rc;
+    if ((rc = dmalloc((void**)&c->part, (size_t)c->max_tiles * n.P * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->lpart, (size_t)c->max_tiles * lpart_w * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->ticket, sizeof(unsigned int)))) {
+        ppo_work_free(c);
+        delete c;
+        return rc;
+    }
+    if (hipMemset(c->ticket, 0, sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        ppo_work_free(c);
+        delete c;
+        return fail(MORL_ERR_HIP, "%s: workspace init failed", nm.algo);
+    }
+    *out = c;
+    return MORL_OK;
+}
+
+// room for a rollout of T x E rows and its rewards and dones copied in; the caller packs the table and then records T and E
+static int ppo_work_rollout(PpoWork& w, const PpoNames& nm, const float* rewards, const float* dones, int T, int E, void* stream) {
+    if (T < 1 || E < 1 || (int64_t)T * E > (int64_t)(1 << 24))
+        return fail(MORL_ERR_ARG, "%s: rollout of %d steps x %d envs (at most %d rows)", nm.algo, T, E, 1 << 24);
+    const int64_t rows = (int64_t)T * E;
+    const int R = w.n.R;
+    if (rows > w.rows_cap) {
+        // (hipFree waits for the work that may still read the old buffers)
+        for (float** p : {&w.table, &w.rewards, &w.dones})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        w.rows_cap = 0; w.T = w.E = 0;
+        int rc;
+        if ((rc = dmalloc((void**)&w.table, (size_t)rows * w.row_w * sizeof(float))) ||
+            (rc = dmalloc((void**)&w.rewards, (size_t)rows * R * sizeof(float))) ||
+            (rc = dmalloc((void**)&w.dones, (size_t)rows * sizeof(float))))
+            return rc;
+        w.rows_cap = rows;
+    }
+    HIP_TRY(hipMemcpyAsync(w.rewards, rewards, (size_t)rows * R * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(w.dones, dones, (size_t)rows * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    return MORL_OK;
+}
+
+// what an update needs of a context; learner >= 0 names ctxs[learner] of a population in the messages
+static int ppo_work_check_update(const PpoWork& w, const PpoNames& nm, int M, int norm_adv, int adam_steps_done, int learner = -1) {
+    char of[32] = "", has[32] = "", at[32] = "";
+    if (learner >= 0) {
+        snprintf(of, sizeof(of), " of ctxs[%d]", learner);
+        snprintf(has, sizeof(has), "ctxs[%d] has ", learner);
+        snprintf(at, sizeof(at), "[%d] =", learner);
+    }
+    if (M < 1 || M > w.max_minibatch)
+        return fail(MORL_ERR_STATE, "%s: minibatch %d outside 1..max_minibatch %d%s", nm.algo, M, w.max_minibatch, of);
+    if (norm_adv && M < 2) return fail(MORL_ERR_ARG, "%s: norm_adv needs a minibatch of at least 2 rows (std of %d)", nm.algo, M);
+    if (w.T < 1) return fail(MORL_ERR_STATE, "%s: %sno rollout (%s_set_rollout)", nm.algo, has, nm.abi);
+    if (!w.have_gae) return fail(MORL_ERR_STATE, "%s: the rollout%s has no advantages yet (%s_gae)", nm.algo, of, nm.abi);
+    if (adam_steps_done < 0) return fail(MORL_ERR_ARG, "adam_steps_done%s %d", at, adam_steps_done);
+    return MORL_OK;
+}
+
+// the fields of a step's argument block that every learner of a call shares
+static void ppo_step_scalars(PpoStepArgs& a, const PpoWork& w, int M, double clip_coef, double ent_coef, double vf_coef,
+                             double max_grad_norm, int clip_vloss, int norm_adv) {
+    a.n = w.n;
+    a.row_w = w.row_w;
+    a.M = M; a.ntiles = (M + PPO_TB - 1) / PPO_TB;
+    a.clip_lo = (float)(1.0 - clip_coef); a.clip_hi = (float)(1.0 + clip_coef); a.clip_coef = (float)clip_coef;
+    a.ent_coef = (float)ent_coef; a.vf_coef = (float)vf_coef; a.max_grad_norm = (float)max_grad_norm;
+    a.clip_vloss = clip_vloss ? 1 : 0; a.norm_adv = norm_adv ? 1 : 0;
+    a.inv_M = (float)(1.0 / M); a.inv_MR = (float)(1.0 / ((double)M * w.n.R)); a.inv_Mm1 = M > 1 ? (float)(1.0 / (M - 1)) : 0.0f;
+    a.fM = (float)M; a.fMR = (float)((double)M * w.n.R);
+    a.one_minus_b1 = (float)(1.0 - 0.9); a.b2 = (float)0.999; a.one_minus_b2 = (float)(1.0 - 0.999); a.eps = 1e-5f;
+}
+
+// Adam's bias corrections of step `step` (1-based) for betas (0.9, 0.999), in float64 as torch forms them
+static void ppo_adam_bias(double lr, int step, float& neg_step_size, float& bc2_sqrt) {
+    neg_step_size = (float)(-(lr / (1.0 - std::pow(0.9, step))));
+    bc2_sqrt = (float)std::sqrt(1.0 - std::pow(0.999, step));
+}
+
+// a single learner's call: the shared fields and the per-learner ones that do not change from step to step
+static void ppo_single_step_args(PpoStepArgs& a, const PpoWork& w, float* params, float* exp_avg, float* exp_avg_sq, int M,
+                                 double clip_coef, double ent_coef, double vf_coef, double max_grad_norm, int clip_vloss,
+                                 int norm_adv) {
+    ppo_step_scalars(a, w, M, clip_coef, ent_coef, vf_coef, max_grad_norm, clip_vloss, norm_adv);
+    a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
+    a.table = w.table; a.table_rows = w.T * w.E;
+    a.part = w.part; a.lpart = w.lpart; a.ticket = w.ticket;
+}
+
 extern "C" int morl_ppo_destroy(morl_ppo_ctx* c) {
     if (!c) return MORL_OK;
-    for (void* p : {(void*)c->table, (void*)c->rewards, (void*)c->dones, (void*)c->part, (void*)c->lpart, (void*)c->ticket})
-        if (p) (void)hipFree(p);
+    ppo_work_free(c);
     delete c;
     return MORL_OK;
 }
@@ -2362,55 +2478,20 @@ extern "C" int morl_ppo_create(morl_ppo_ctx** out, int obs_dim, int action_dim, 
     if (!out) return fail(MORL_ERR_ARG, "out is NULL");
     *out = nullptr;
     PpoNet n{};
-    int rc = ppo_fill(n, obs_dim, action_dim, reward_dim, n_hidden, hidden0, hidden1);
+    const int rc = ppo_fill(n, obs_dim, action_dim, reward_dim, n_hidden, hidden0, hidden1);
     if (rc) return rc;
-    if (max_minibatch < 1 || max_minibatch > (1 << 20))
-        return fail(MORL_ERR_ARG, "MO-PPO: max_minibatch %d outside 1..%d", max_minibatch, 1 << 20);
-    morl_ppo_ctx* c = new (std::nothrow) morl_ppo_ctx();
-    if (!c) return fail(MORL_ERR_ALLOC, "out of host memory");
-    c->n = n;
-    c->max_minibatch = max_minibatch;
-    c->max_tiles = (max_minibatch + PPO_TB - 1) / PPO_TB;
-    c->row_w = obs_dim + action_dim + 2 + 2 * reward_dim;
-    if ((rc = dmalloc((void**)&c->part, (size_t)c->max_tiles * n.P * sizeof(float))) ||
-        (rc = dmalloc((void**)&c->lpart, (size_t)c->max_tiles * PPO_NPART * sizeof(float))) ||
-        (rc = dmalloc((void**)&c->ticket, sizeof(unsigned int)))) {
-        morl_ppo_destroy(c);
-        return rc;
-    }
-    if (hipMemset(c->ticket, 0, sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        morl_ppo_destroy(c);
-        return fail(MORL_ERR_HIP, "MO-PPO: workspace init failed");
-    }
-    *out = c;
-    return MORL_OK;
+    return ppo_work_create(out, PPO_NAMES, n, max_minibatch, obs_dim + action_dim + 2 + 2 * reward_dim, PPO_NPART);
 }
 
 extern "C" int morl_ppo_set_rollout(morl_ppo_ctx* c, const float* obs, const float* actions, const float* logprobs,
                                     const float* rewards, const float* dones, const float* values, int T, int E, void* stream) {
     if (!c || !obs || !actions || !logprobs || !rewards || !dones || !values) return fail(MORL_ERR_ARG, "NULL argument");
-    if (T < 1 || E < 1 || (int64_t)T * E > (int64_t)(1 << 24))
-        return fail(MORL_ERR_ARG, "MO-PPO: rollout of %d steps x %d envs (at most %d rows)", T, E, 1 << 24);
-    const int64_t rows = (int64_t)T * E;
-    const int R = c->n.R;
-    if (rows > c->rows_cap) {
-        // (hipFree waits for the work that may still read the old buffers)
-        for (float** p : {&c->table, &c->rewards, &c->dones})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        c->rows_cap = 0; c->T = c->E = 0;
-        int rc;
-        if ((rc = dmalloc((void**)&c->table, (size_t)rows * c->row_w * sizeof(float))) ||
-            (rc = dmalloc((void**)&c->rewards, (size_t)rows * R * sizeof(float))) ||
-            (rc = dmalloc((void**)&c->dones, (size_t)rows * sizeof(float))))
-            return rc;
-        c->rows_cap = rows;
-    }
-    HIP_TRY(hipMemcpyAsync(c->rewards, rewards, (size_t)rows * R * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
-    HIP_TRY(hipMemcpyAsync(c->dones, dones, (size_t)rows * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
-    const int64_t total = rows * c->row_w;
+    const int rc = ppo_work_rollout(*c, PPO_NAMES, rewards, dones, T, E, stream);
+    if (rc) return rc;
+    const int64_t rows = (int64_t)T * E, total = rows * c->row_w;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 1024);
-    hipLaunchKernelGGL(ppo_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c->n.D, c->n.A, R, c->row_w, (int)rows, obs,
-                       actions, logprobs, values, c->table);
+    hipLaunchKernelGGL(ppo_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c->n.D, c->n.A, c->n.R, c->row_w, (int)rows,
+                       obs, actions, logprobs, values, c->table);
     LAUNCH_CHECK("ppo_pack");
     c->T = T; c->E = E; c->have_gae = 0;
     return MORL_OK;
@@ -2433,29 +2514,12 @@ extern "C" int morl_ppo_update_n(morl_ppo_ctx* c, float* params, float* exp_avg,
                                  double max_grad_norm, int clip_vloss, int norm_adv, float* stats_out, void* stream) {
     if (!c || !params || !exp_avg || !exp_avg_sq || !idx || !stats_out) return fail(MORL_ERR_ARG, "NULL argument");
     if (n < 1) return fail(MORL_ERR_ARG, "n = %d updates", n);
-    if (M < 1 || M > c->max_minibatch)
-        return fail(MORL_ERR_STATE, "MO-PPO: minibatch %d outside 1..max_minibatch %d", M, c->max_minibatch);
-    if (norm_adv && M < 2) return fail(MORL_ERR_ARG, "MO-PPO: norm_adv needs a minibatch of at least 2 rows (std of %d)", M);
-    if (c->T < 1) return fail(MORL_ERR_STATE, "MO-PPO: no rollout (morl_ppo_set_rollout)");
-    if (!c->have_gae) return fail(MORL_ERR_STATE, "MO-PPO: the rollout has no advantages yet (morl_ppo_gae)");
-    if (adam_steps_done < 0) return fail(MORL_ERR_ARG, "adam_steps_done %d", adam_steps_done);
+    const int rc = ppo_work_check_update(*c, PPO_NAMES, M, norm_adv, adam_steps_done);
+    if (rc) return rc;
     PpoStepArgs a{};
-    a.n = c->n;
-    a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
-    a.table = c->table; a.table_rows = c->T * c->E; a.row_w = c->row_w;
-    a.M = M; a.ntiles = (M + PPO_TB - 1) / PPO_TB;
-    a.part = c->part; a.lpart = c->lpart; a.ticket = c->ticket;
-    a.clip_lo = (float)(1.0 - clip_coef); a.clip_hi = (float)(1.0 + clip_coef); a.clip_coef = (float)clip_coef;
-    a.ent_coef = (float)ent_coef; a.vf_coef = (float)vf_coef; a.max_grad_norm = (float)max_grad_norm;
-    a.clip_vloss = clip_vloss ? 1 : 0; a.norm_adv = norm_adv ? 1 : 0;
-    a.inv_M = (float)(1.0 / M); a.inv_MR = (float)(1.0 / ((double)M * c->n.R)); a.inv_Mm1 = M > 1 ? (float)(1.0 / (M - 1)) : 0.0f;
-    a.fM = (float)M; a.fMR = (float)((double)M * c->n.R);
-    const double b1 = 0.9, b2 = 0.999;
-    a.one_minus_b1 = (float)(1.0 - b1); a.b2 = (float)b2; a.one_minus_b2 = (float)(1.0 - b2); a.eps = 1e-5f;
+    ppo_single_step_args(a, *c, params, exp_avg, exp_avg_sq, M, clip_coef, ent_coef, vf_coef, max_grad_norm, clip_vloss, norm_adv);
     for (int k = 0; k < n; ++k) {
-        const int step = adam_steps_done + k + 1;
-        a.neg_step_size = (float)(-(lr / (1.0 - std::pow(b1, step))));
-        a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, step));
+        ppo_adam_bias(lr, adam_steps_done + k + 1, a.neg_step_size, a.bc2_sqrt);
         a.idx = idx + (size_t)k * M;
         a.stats_out = stats_out + (size_t)k * PPO_NSTATS;
         hipLaunchKernelGGL(ppo_step_kernel, dim3(a.ntiles), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
@@ -2516,41 +2580,23 @@ extern "C" int morl_ppo_update_n_pop(int P, morl_ppo_ctx* const* ctxs, float* co
     if (!lr || !adam_steps_done) return fail(MORL_ERR_ARG, "MO-PPO update_n_pop: lr / adam_steps_done is NULL");
     if (n < 1) return fail(MORL_ERR_ARG, "n = %d updates", n);
     if (norm_adv && M < 2) return fail(MORL_ERR_ARG, "MO-PPO: norm_adv needs a minibatch of at least 2 rows (std of %d)", M);
-    for (int i = 0; i < P; ++i) {
-        const morl_ppo_ctx* c = ctxs[i];
-        if (M < 1 || M > c->max_minibatch)
-            return fail(MORL_ERR_STATE, "MO-PPO: minibatch %d outside 1..max_minibatch %d of ctxs[%d]", M, c->max_minibatch, i);
-        if (c->T < 1) return fail(MORL_ERR_STATE, "MO-PPO: ctxs[%d] has no rollout (morl_ppo_set_rollout)", i);
-        if (!c->have_gae) return fail(MORL_ERR_STATE, "MO-PPO: the rollout of ctxs[%d] has no advantages yet (morl_ppo_gae)", i);
-        if (adam_steps_done[i] < 0) return fail(MORL_ERR_ARG, "adam_steps_done[%d] = %d", i, adam_steps_done[i]);
-    }
-    const morl_ppo_ctx* c0 = ctxs[0];
+    for (int i = 0; i < P; ++i)
+        if ((rc = ppo_work_check_update(*ctxs[i], PPO_NAMES, M, norm_adv, adam_steps_done[i], i))) return rc;
     PpoPopStepArgs a{};
-    a.s.n = c0->n;
-    a.s.row_w = c0->row_w;
-    a.s.M = M; a.s.ntiles = (M + PPO_TB - 1) / PPO_TB;
-    a.s.clip_lo = (float)(1.0 - clip_coef); a.s.clip_hi = (float)(1.0 + clip_coef); a.s.clip_coef = (float)clip_coef;
-    a.s.ent_coef = (float)ent_coef; a.s.vf_coef = (float)vf_coef; a.s.max_grad_norm = (float)max_grad_norm;
-    a.s.clip_vloss = clip_vloss ? 1 : 0; a.s.norm_adv = norm_adv ? 1 : 0;
-    a.s.inv_M = (float)(1.0 / M); a.s.inv_MR = (float)(1.0 / ((double)M * c0->n.R)); a.s.inv_Mm1 = M > 1 ? (float)(1.0 / (M - 1)) : 0.0f;
-    a.s.fM = (float)M; a.s.fMR = (float)((double)M * c0->n.R);
-    const double b1 = 0.9, b2 = 0.999;
-    a.s.one_minus_b1 = (float)(1.0 - b1); a.s.b2 = (float)b2; a.s.one_minus_b2 = (float)(1.0 - b2); a.s.eps = 1e-5f;
+    ppo_step_scalars(a.s, *ctxs[0], M, clip_coef, ent_coef, vf_coef, max_grad_norm, clip_vloss, norm_adv);
     for (int k = 0; k < n; ++k) {
         for (int p0 = 0; p0 < P; p0 += PPO_POP_CHUNK) {
             const int pc = std::min(PPO_POP_CHUNK, P - p0);
             for (int j = 0; j < pc; ++j) {
                 const int i = p0 + j;
                 const morl_ppo_ctx* c = ctxs[i];
-                const int step = adam_steps_done[i] + k + 1;
                 PpoLearner& l = a.l[j];
                 l.params = params[i]; l.exp_avg = exp_avg[i]; l.exp_avg_sq = exp_avg_sq[i];
                 l.table = c->table; l.table_rows = c->T * c->E;
                 l.idx = idx[i] + (size_t)k * M;
                 l.part = c->part; l.lpart = c->lpart; l.ticket = c->ticket;
                 l.stats_out = stats_out[i] + (size_t)k * PPO_NSTATS;
-                l.neg_step_size = (float)(-(lr[i] / (1.0 - std::pow(b1, step))));
-                l.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, step));
+                ppo_adam_bias(lr[i], adam_steps_done[i] + k + 1, l.neg_step_size, l.bc2_sqrt);
             }
             hipLaunchKernelGGL(ppo_pop_step_kernel, dim3(a.s.ntiles, pc), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
             LAUNCH_CHECK("ppo_pop_step");
@@ -2629,18 +2675,8 @@ extern "C" int morl_ppo_gae_pop(int P, morl_ppo_ctx* const* ctxs, const float* c
 // =====================================================================================================================
 #include "nlppo_kernels.h"
 
-struct morl_nlppo_ctx {
-    PpoNet n{};                    // n.D = obs_dim + reward_dim + pref_dim
+struct morl_nlppo_ctx : PpoWork {  // n.D = obs_dim + reward_dim + pref_dim
     NlppoIn in{};
-    int max_minibatch = 0, max_tiles = 0, row_w = 0;
-    float* table = nullptr;        // [rows_cap][row_w]
-    float* rewards = nullptr;      // [rows_cap][R]
-    float* dones = nullptr;        // [rows_cap]
-    int64_t rows_cap = 0;
-    int T = 0, E = 0, have_gae = 0;
-    float* part = nullptr;         // [max_tiles][P]
-    float* lpart = nullptr;        // [max_tiles][NLPPO_NPART]
-    unsigned int* ticket = nullptr;
 };
 
 static int nlppo_fill(PpoNet& n, NlppoIn& in, int obs_dim, int A, int R, int pref_dim, int nh, int h0, int h1) {
@@ -2651,34 +2687,8 @@ static int nlppo_fill(PpoNet& n, NlppoIn& in, int obs_dim, int A, int R, int pre
         return fail(MORL_ERR_ARG, "NL-MO-PPO: input width obs_dim %d + reward_dim %d + pref_dim %d exceeds %d", obs_dim, R, pref_dim,
                     PPO_MAX_D);
     if (A < 2 || A > PPO_MAX_A) return fail(MORL_ERR_ARG, "NL-MO-PPO: n_actions %d outside 2..%d", A, PPO_MAX_A);
-    if (nh < 1 || nh > 2) return fail(MORL_ERR_ARG, "NL-MO-PPO: n_hidden %d is not 1 or 2 hidden layers", nh);
-    const int hs[2] = {h0, h1};
-    for (int l = 0; l < nh; ++l)
-        if (hs[l] < 32 || hs[l] > PPO_MAX_H || hs[l] % 32 != 0)
-            return fail(MORL_ERR_ARG, "NL-MO-PPO: hidden width %d (layer %d) is not one of 32, 64, 96, 128", hs[l], l);
-    const int D = obs_dim + R + pref_dim;
     in.obs_dim = obs_dim; in.pref_dim = pref_dim;
-    n.D = D; n.A = A; n.R = R; n.nh = nh; n.H1 = h0; n.H2 = (nh == 2) ? h1 : h0;
-    n.oLs = 0;
-    int o = 0, t = 0;
-    auto take = [&](int count) { const int at = o; n.tstart[t++] = o; o += count; return at; };
-    for (int which = 0; which < 2; ++which) {
-        PpoMlp& m = which ? n.a : n.c;
-        const int N = which ? A : R;
-        m.oW0 = take(n.H1 * D);
-        m.ob0 = take(n.H1);
-        m.oW1 = m.ob1 = 0;
-        if (nh == 2) {
-            m.oW1 = take(n.H2 * n.H1);
-            m.ob1 = take(n.H2);
-        }
-        m.oWo = take(N * n.H2);
-        m.obo = take(N);
-    }
-    n.P = o;
-    n.ntensors = t;
-    for (int i = t; i <= PPO_MAX_TENSORS; ++i) n.tstart[i] = o;
-    return MORL_OK;
+    return ppo_layout(n, "NL-MO-PPO", false, obs_dim + R + pref_dim, A, R, nh, h0, h1);
 }
 
 extern "C" int64_t morl_nlppo_param_count(int obs_dim, int n_actions, int reward_dim, int pref_dim, int n_hidden, int hidden0,
@@ -2690,8 +2700,7 @@ extern "C" int64_t morl_nlppo_param_count(int obs_dim, int n_actions, int reward
 
 extern "C" int morl_nlppo_destroy(morl_nlppo_ctx* c) {
     if (!c) return MORL_OK;
-    for (void* p : {(void*)c->table, (void*)c->rewards, (void*)c->dones, (void*)c->part, (void*)c->lpart, (void*)c->ticket})
-        if (p) (void)hipFree(p);
+    ppo_work_free(c);
     delete c;
     return MORL_OK;
 }
@@ -2704,26 +2713,8 @@ extern "C" int morl_nlppo_create(morl_nlppo_ctx** out, int obs_dim, int n_action
     NlppoIn in{};
     int rc = nlppo_fill(n, in, obs_dim, n_actions, reward_dim, pref_dim, n_hidden, hidden0, hidden1);
     if (rc) return rc;
-    if (max_minibatch < 1 || max_minibatch > (1 << 20))
-        return fail(MORL_ERR_ARG, "NL-MO-PPO: max_minibatch %d outside 1..%d", max_minibatch, 1 << 20);
-    morl_nlppo_ctx* c = new (std::nothrow) morl_nlppo_ctx();
-    if (!c) return fail(MORL_ERR_ALLOC, "out of host memory");
-    c->n = n;
-    c->in = in;
-    c->max_minibatch = max_minibatch;
-    c->max_tiles = (max_minibatch + PPO_TB - 1) / PPO_TB;
-    c->row_w = n.D + 2 + 3 * reward_dim;
-    if ((rc = dmalloc((void**)&c->part, (size_t)c->max_tiles * n.P * sizeof(float))) ||
-        (rc = dmalloc((void**)&c->lpart, (size_t)c->max_tiles * NLPPO_NPART * sizeof(float))) ||
-        (rc = dmalloc((void**)&c->ticket, sizeof(unsigned int)))) {
-        morl_nlppo_destroy(c);
-        return rc;
-    }
-    if (hipMemset(c->ticket, 0, sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        morl_nlppo_destroy(c);
-        return fail(MORL_ERR_HIP, "NL-MO-PPO: workspace init failed");
-    }
-    *out = c;
+    if ((rc = ppo_work_create(out, NLPPO_NAMES, n, max_minibatch, n.D + 2 + 3 * reward_dim, NLPPO_NPART))) return rc;
+    (*out)->in = in;
     return MORL_OK;
 }
 
@@ -2731,28 +2722,13 @@ extern "C" int morl_nlppo_set_rollout(morl_nlppo_ctx* c, const float* obs, const
                                       const float* logprobs, const float* rewards, const float* dones, const float* values,
                                       const float* pref, int T, int E, void* stream) {
     if (!c || !obs || !acc_rewards || !actions || !logprobs || !rewards || !dones || !values) return fail(MORL_ERR_ARG, "NULL argument");
-    if (T < 1 || E < 1 || (int64_t)T * E > (int64_t)(1 << 24))
-        return fail(MORL_ERR_ARG, "NL-MO-PPO: rollout of %d steps x %d envs (at most %d rows)", T, E, 1 << 24);
-    const int64_t rows = (int64_t)T * E;
-    const int R = c->n.R;
-    if (rows > c->rows_cap) {
-        // (hipFree waits for the work that may still read the old buffers)
-        for (float** p : {&c->table, &c->rewards, &c->dones})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        c->rows_cap = 0; c->T = c->E = 0;
-        int rc;
-        if ((rc = dmalloc((void**)&c->table, (size_t)rows * c->row_w * sizeof(float))) ||
-            (rc = dmalloc((void**)&c->rewards, (size_t)rows * R * sizeof(float))) ||
-            (rc = dmalloc((void**)&c->dones, (size_t)rows * sizeof(float))))
-            return rc;
-        c->rows_cap = rows;
-    }
-    HIP_TRY(hipMemcpyAsync(c->rewards, rewards, (size_t)rows * R * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
-    HIP_TRY(hipMemcpyAsync(c->dones, dones, (size_t)rows * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
-    const int64_t total = rows * c->row_w;
+    const int rc = ppo_work_rollout(*c, NLPPO_NAMES, rewards, dones, T, E, stream);
+    if (rc) return rc;
+    const int64_t rows = (int64_t)T * E, total = rows * c->row_w;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 1024);
-    hipLaunchKernelGGL(nlppo_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c->in.obs_dim, R, c->in.pref_dim, c->row_w,
-                       (int)rows, obs, acc_rewards, (const int*)actions, logprobs, values, c->in.pref_dim ? pref : nullptr, c->table);
+    hipLaunchKernelGGL(nlppo_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c->in.obs_dim, c->n.R, c->in.pref_dim,
+                       c->row_w, (int)rows, obs, acc_rewards, (const int*)actions, logprobs, values, c->in.pref_dim ? pref : nullptr,
+                       c->table);
     LAUNCH_CHECK("nlppo_pack");
     c->T = T; c->E = E; c->have_gae = 0;
     return MORL_OK;
@@ -2776,33 +2752,16 @@ extern "C" int morl_nlppo_update_n(morl_nlppo_ctx* c, float* params, float* exp_
                                    float* stats_out, void* stream) {
     if (!c || !params || !exp_avg || !exp_avg_sq || !idx || !loss_weights || !stats_out) return fail(MORL_ERR_ARG, "NULL argument");
     if (n < 1) return fail(MORL_ERR_ARG, "n = %d updates", n);
-    if (M < 1 || M > c->max_minibatch)
-        return fail(MORL_ERR_STATE, "NL-MO-PPO: minibatch %d outside 1..max_minibatch %d", M, c->max_minibatch);
-    if (norm_adv && M < 2) return fail(MORL_ERR_ARG, "NL-MO-PPO: norm_adv needs a minibatch of at least 2 rows (std of %d)", M);
-    if (c->T < 1) return fail(MORL_ERR_STATE, "NL-MO-PPO: no rollout (morl_nlppo_set_rollout)");
-    if (!c->have_gae) return fail(MORL_ERR_STATE, "NL-MO-PPO: the rollout has no advantages yet (morl_nlppo_gae)");
-    if (adam_steps_done < 0) return fail(MORL_ERR_ARG, "adam_steps_done %d", adam_steps_done);
+    const int rc = ppo_work_check_update(*c, NLPPO_NAMES, M, norm_adv, adam_steps_done);
+    if (rc) return rc;
     NlppoStepArgs a{};
-    a.n = c->n;
-    a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
-    a.table = c->table; a.table_rows = c->T * c->E; a.row_w = c->row_w;
-    a.M = M; a.ntiles = (M + PPO_TB - 1) / PPO_TB;
+    ppo_single_step_args(a.s, *c, params, exp_avg, exp_avg_sq, M, clip_coef, ent_coef, vf_coef, max_grad_norm, clip_vloss, norm_adv);
     a.loss_weights = loss_weights;
-    a.part = c->part; a.lpart = c->lpart; a.ticket = c->ticket;
-    a.clip_lo = (float)(1.0 - clip_coef); a.clip_hi = (float)(1.0 + clip_coef); a.clip_coef = (float)clip_coef;
-    a.ent_coef = (float)ent_coef; a.vf_coef = (float)vf_coef; a.max_grad_norm = (float)max_grad_norm;
-    a.clip_vloss = clip_vloss ? 1 : 0; a.norm_adv = norm_adv ? 1 : 0;
-    a.inv_M = (float)(1.0 / M); a.inv_MR = (float)(1.0 / ((double)M * c->n.R)); a.inv_Mm1 = M > 1 ? (float)(1.0 / (M - 1)) : 0.0f;
-    a.fM = (float)M; a.fMR = (float)((double)M * c->n.R);
-    const double b1 = 0.9, b2 = 0.999;
-    a.one_minus_b1 = (float)(1.0 - b1); a.b2 = (float)b2; a.one_minus_b2 = (float)(1.0 - b2); a.eps = 1e-5f;
     for (int k = 0; k < n; ++k) {
-        const int step = adam_steps_done + k + 1;
-        a.neg_step_size = (float)(-(lr / (1.0 - std::pow(b1, step))));
-        a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, step));
-        a.idx = idx + (size_t)k * M;
-        a.stats_out = stats_out + (size_t)k * PPO_NSTATS;
-        hipLaunchKernelGGL(nlppo_step_kernel, dim3(a.ntiles), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
+        ppo_adam_bias(lr, adam_steps_done + k + 1, a.s.neg_step_size, a.s.bc2_sqrt);
+        a.s.idx = idx + (size_t)k * M;
+        a.s.stats_out = stats_out + (size_t)k * PPO_NSTATS;
+        hipLaunchKernelGGL(nlppo_step_kernel, dim3(a.s.ntiles), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
         LAUNCH_CHECK("nlppo_step");
     }
     return MORL_OK;

@@ -13,8 +13,8 @@
 // Structure: that of ppo_kernels.h, whose MLP forward / backward, transposed product and tile state are used as they are.  What
 // is new: the categorical head (its entropy back-propagates through the actor, so every row has its own entropy gradient), the
 // [R] advantages of a row with one mean / std per objective, and the per-objective choice of the surrogate's active branch.  The
-// last workgroup's reduction, clip scale and Adam step are a copy of ppo_step_tile's tail without the log-std tensor: the
-// existing kernel is left untouched.
+// value loss, the ticket and the last workgroup's reduction, clip scale and Adam step are ppo_kernels.h's functions, called
+// without the log-std tensor.
 #pragma once
 #include "ppo_kernels.h"
 
@@ -169,28 +169,14 @@ static __global__ __launch_bounds__(64) void nlppo_gae_kernel(int T, int E, int 
 // one minibatch step
 // ---------------------------------------------------------------------------------------------------------------------
 struct NlppoStepArgs {
-    PpoNet n;                      // D = D_in; oLs is not used
-    float* params;                 // [P]  read by every tile, stepped by the last workgroup
-    float* exp_avg;                // [P]
-    float* exp_avg_sq;             // [P]
-    const float* table;            // [table_rows][row_w]
-    int table_rows, row_w;
-    const int* idx;                // [M] rows of the table, this step's minibatch
-    int M, ntiles;
+    PpoStepArgs s;                 // n.D = D_in, n.oLs is not used; lpart is [ntiles][NLPPO_NPART]
     const float* loss_weights;     // [R]
-    float* part;                   // [ntiles][P] gradient partials
-    float* lpart;                  // [ntiles][NLPPO_NPART] loss partial sums
-    unsigned int* ticket;          // arrival counter, zero between launches
-    float* stats_out;              // [PPO_NSTATS]
-    float clip_lo, clip_hi, clip_coef, ent_coef, vf_coef, max_grad_norm;
-    int clip_vloss, norm_adv;
-    float inv_M, inv_MR, inv_Mm1, fM, fMR;
-    float one_minus_b1, b2, one_minus_b2, neg_step_size, bc2_sqrt, eps;
 };
 
-static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoStepArgs a) {
+static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoStepArgs args) {
     __shared__ NlppoLds S;
     PpoLds& L = S.p;
+    const PpoStepArgs& a = args.s;
     const PpoNet& n = a.n;
     const int tid = (int)threadIdx.x, tile = (int)blockIdx.x, row0 = tile * PPO_TB;
     const int valid = min(PPO_TB, a.M - row0);
@@ -202,7 +188,7 @@ static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoSte
         const int r = o / n.D, d = o - r * n.D;
         float v = 0.0f;
         if (r < valid) {
-            const int row = min(max(a.idx[row0 + r], 0), a.table_rows - 1);
+            const int row = ppo_table_row(a.idx, row0 + r, a.table_rows);
             v = a.table[(size_t)row * a.row_w + d];
         }
         L.x[o] = v;
@@ -211,7 +197,7 @@ static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoSte
         const int r = o / n.R, k = o - r * n.R;
         float adv = 0.0f, ret = 0.0f, ov = 0.0f;
         if (r < valid) {
-            const int row = min(max(a.idx[row0 + r], 0), a.table_rows - 1);
+            const int row = ppo_table_row(a.idx, row0 + r, a.table_rows);
             adv = a.table[(size_t)row * a.row_w + adv_col + k];
             ret = a.table[(size_t)row * a.row_w + ro + k];
             ov = a.table[(size_t)row * a.row_w + vo + k];
@@ -224,14 +210,14 @@ static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoSte
         float lp = 0.0f;
         int act = 0;
         if (tid < valid) {
-            const int row = min(max(a.idx[row0 + tid], 0), a.table_rows - 1);
+            const int row = ppo_table_row(a.idx, row0 + tid, a.table_rows);
             lp = a.table[(size_t)row * a.row_w + lo];
             act = min(max((int)a.table[(size_t)row * a.row_w + ac], 0), n.A - 1);
         }
         L.row[tid * 4] = lp;
         S.action[tid] = act;
     }
-    if (tid < PPO_MAX_R) S.w[tid] = (tid < n.R) ? a.loss_weights[tid] : 0.0f;
+    if (tid < PPO_MAX_R) S.w[tid] = (tid < n.R) ? args.loss_weights[tid] : 0.0f;
 
     // ---- advantage normalisation (nl_mo_ppo.py:366-369): per objective the mean and unbiased std of all M advantages, read in
     // minibatch order; objective k belongs to the work-items [32 k, 32 k + 32), whose sums meet in a fixed tree
@@ -240,14 +226,14 @@ static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoSte
         float s = 0.0f;
         if (k < n.R)
             for (int b = lane; b < a.M; b += NLPPO_SEG) {
-                const int row = min(max(a.idx[b], 0), a.table_rows - 1);
+                const int row = ppo_table_row(a.idx, b, a.table_rows);
                 s = __fadd_rn(s, a.table[(size_t)row * a.row_w + adv_col + k]);
             }
         const float mean = __fdiv_rn(nlppo_seg_sum(L.red, s), a.fM);
         float q = 0.0f;
         if (k < n.R)
             for (int b = lane; b < a.M; b += NLPPO_SEG) {
-                const int row = min(max(a.idx[b], 0), a.table_rows - 1);
+                const int row = ppo_table_row(a.idx, b, a.table_rows);
                 const float dlt = __fsub_rn(a.table[(size_t)row * a.row_w + adv_col + k], mean);
                 q = fmaf(dlt, dlt, q);
             }
@@ -261,36 +247,9 @@ static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoSte
 
     float* part = a.part + (size_t)tile * n.P;
 
-    // ---- critic: forward, value loss (nl_mo_ppo.py:378-385) and its gradient, backward -- as ppo_step_tile has them
+    // ---- critic: forward, value loss (nl_mo_ppo.py:378-385) and its gradient, backward
     ppo_mlp_forward(L, n, n.c, p, n.R);
-    if (tid < PPO_TB) {
-        const int r = tid;
-        float vsum = 0.0f;
-        const float gscale = __fmul_rn(__fmul_rn(0.5f, a.vf_coef), a.inv_MR);
-        for (int k = 0; k < n.R; ++k) {
-            const float v = L.out[r * n.R + k], ret = L.ret[r * n.R + k], ov = L.oldv[r * n.R + k];
-            float g = 0.0f;
-            if (r < valid) {
-                const float du = __fsub_rn(v, ret);
-                const float u = __fmul_rn(du, du);
-                g = __fmul_rn(2.0f, du);
-                float m = u;
-                if (a.clip_vloss) {
-                    const float dv = __fsub_rn(v, ov);
-                    const float vc = __fadd_rn(ov, fminf(fmaxf(dv, -a.clip_coef), a.clip_coef));
-                    const float dc = __fsub_rn(vc, ret);
-                    const float cl = __fmul_rn(dc, dc);
-                    m = fmaxf(u, cl);
-                    // inside the range both branches have the derivative 2 (v - ret); outside, the clipped branch has none
-                    const bool inside = dv >= -a.clip_coef && dv <= a.clip_coef;
-                    if (!inside) g = (u > cl) ? g : ((u == cl) ? du : 0.0f);
-                }
-                vsum = __fadd_rn(vsum, m);
-            }
-            L.dout[r * n.R + k] = __fmul_rn(g, gscale);
-        }
-        S.rs[r * NLPPO_NPART + PPO_MAX_R] = vsum;
-    }
+    if (tid < PPO_TB) S.rs[tid * NLPPO_NPART + PPO_MAX_R] = ppo_value_loss_row(L, a, tid, valid);
     __syncthreads();
     ppo_mlp_backward(L, n, n.c, p, part, n.R);
 
@@ -357,49 +316,11 @@ static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoSte
     }
     ppo_mlp_backward(L, n, n.a, p, part, n.A);
 
-    // ---- the last workgroup to arrive owns the step (a copy of ppo_step_tile's tail without the log-std tensor)
-    __threadfence();
-    __syncthreads();
+    // ---- the last workgroup to arrive owns the step
+    if (!pcn_last_arrival(a.ticket, a.ntiles, L.last)) return;
+    const PpoLearner l = ppo_own_learner(a);
+    const float total = ppo_grad_clip(L, a, l, false);
     if (tid == 0) {
-        const unsigned int prev = atomicAdd(a.ticket, 1u);
-        L.last = (prev + 1u == (unsigned int)a.ntiles) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!L.last) return;
-    __threadfence();
-
-    // the gradient: partials summed in tile order (four loads in flight, added in order), kept in tile 0's slot
-    float* grad = a.part;
-    for (int t = 0; t < n.ntensors; ++t) {
-        float sq = 0.0f;
-        for (int q = n.tstart[t] + tid; q < n.tstart[t + 1]; q += PPO_THREADS) {
-            float g = a.part[q];
-            int tl = 1;
-            for (; tl + 4 <= a.ntiles; tl += 4) {
-                const float g0 = a.part[(size_t)tl * n.P + q], g1 = a.part[(size_t)(tl + 1) * n.P + q];
-                const float g2 = a.part[(size_t)(tl + 2) * n.P + q], g3 = a.part[(size_t)(tl + 3) * n.P + q];
-                g = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(g, g0), g1), g2), g3);
-            }
-            for (; tl < a.ntiles; ++tl) g = __fadd_rn(g, a.part[(size_t)tl * n.P + q]);
-            grad[q] = g;
-            sq = fmaf(g, g, sq);
-        }
-        L.w[t * PPO_THREADS + tid] = sq;
-    }
-    __syncthreads();
-    // clip_grad_norm_ (nl_mo_ppo.py:392): the 2-norm of the per-tensor 2-norms; scale = max_norm / (total + 1e-6) clamped to 1
-    if (tid < n.ntensors) {
-        float s = 0.0f;
-        for (int i = 0; i < PPO_THREADS; ++i) s = __fadd_rn(s, L.w[tid * PPO_THREADS + i]);
-        L.red[tid] = __fsqrt_rn(s);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float s = 0.0f;
-        for (int t = 0; t < n.ntensors; ++t) s = fmaf(L.red[t], L.red[t], s);
-        const float total = __fsqrt_rn(s);
-        L.stat[2] = fminf(__fdiv_rn(a.max_grad_norm, __fadd_rn(total, 1e-6f)), 1.0f);
-        L.stat[3] = total;
         *a.ticket = 0u;                                        // re-armed for the next launch on the stream
         float ls[NLPPO_NPART];
         for (int i = 0; i < NLPPO_NPART; ++i) ls[i] = 0.0f;
@@ -419,18 +340,7 @@ static __global__ __launch_bounds__(PPO_THREADS) void nlppo_step_kernel(NlppoSte
         a.stats_out[7] = total;
     }
     __syncthreads();
-    const float scale = L.stat[2];
-    // torch _single_tensor_adam with eps 1e-5 (nl_mo_ppo.py:222, 393): lerp_, mul_ + addcmul_, addcdiv_
-    for (int q = tid; q < n.P; q += PPO_THREADS) {
-        const float g = __fmul_rn(grad[q], scale);
-        float m = a.exp_avg[q], v = a.exp_avg_sq[q];
-        m = fmaf(a.one_minus_b1, __fsub_rn(g, m), m);
-        v = __fadd_rn(__fmul_rn(v, a.b2), __fmul_rn(__fmul_rn(a.one_minus_b2, g), g));
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), a.bc2_sqrt), a.eps);
-        a.params[q] = __fadd_rn(a.params[q], __fmul_rn(a.neg_step_size, __fdiv_rn(m, denom)));
-        a.exp_avg[q] = m;
-        a.exp_avg_sq[q] = v;
-    }
+    ppo_adam_sweep(L, a, l);
 }
 
 }  // namespace morl

@@ -185,6 +185,35 @@ __device__ __forceinline__ void pcn_db(float* __restrict__ dst, const float* dz,
     }
 }
 
+// The ticket (shared with ppo_kernels.h / nlppo_kernels.h): a workgroup fences what it wrote, work-item 0 draws a ticket and tells
+// the others through LDS (`last`) whether it was the last of `ntiles`.  True in every work-item of that one workgroup, which has
+// fenced again and may read what the others wrote; whoever re-arms the ticket is its caller.
+__device__ __forceinline__ bool pcn_last_arrival(unsigned int* ticket, int ntiles, int& last) {
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int prev = atomicAdd(ticket, 1u);
+        last = (prev + 1u == (unsigned int)ntiles) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!last) return false;
+    __threadfence();
+    return true;
+}
+
+// torch _single_tensor_adam on one element with the gradient g: lerp_, mul_ + addcmul_, addcdiv_ -- the operation order of
+// optim_kernels.h.  neg_step_size = -lr / (1 - b1^t) and bc2_sqrt = sqrt(1 - b2^t) are formed on the host in float64.
+__device__ __forceinline__ void pcn_adam(float g, float& param, float& exp_avg, float& exp_avg_sq, float one_minus_b1, float b2,
+                                         float one_minus_b2, float neg_step_size, float bc2_sqrt, float eps) {
+    float m = exp_avg, v = exp_avg_sq;
+    m = fmaf(one_minus_b1, __fsub_rn(g, m), m);
+    v = __fadd_rn(__fmul_rn(v, b2), __fmul_rn(__fmul_rn(one_minus_b2, g), g));
+    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bc2_sqrt), eps);
+    param = __fadd_rn(param, __fmul_rn(neg_step_size, __fdiv_rn(m, denom)));
+    exp_avg = m;
+    exp_avg_sq = v;
+}
+
 static __global__ __launch_bounds__(PCN_THREADS) void pcn_step_kernel(PcnStepArgs a) {
     __shared__ PcnLds L;
     const PcnNet& n = a.n;
@@ -305,15 +334,7 @@ static __global__ __launch_bounds__(PCN_THREADS) void pcn_step_kernel(PcnStepArg
     pcn_db(part + n.obc, L.h, H, H);
 
     // ---- the last workgroup to arrive owns the step
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned int prev = atomicAdd(a.ticket, 1u);
-        L.last = (prev + 1u == (unsigned int)a.ntiles) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!L.last) return;
-    __threadfence();
+    if (!pcn_last_arrival(a.ticket, a.ntiles, L.last)) return;
     if (tid == 0) {
         *a.ticket = 0u;                                        // re-armed for the next launch on the stream
         float loss = 0.0f, ent = 0.0f;
@@ -321,17 +342,12 @@ static __global__ __launch_bounds__(PCN_THREADS) void pcn_step_kernel(PcnStepArg
         *a.loss_out = __fmul_rn(loss, a.inv_count);
         if (a.ent_out != nullptr) *a.ent_out = ent;
     }
-    // torch _single_tensor_adam (pcn.py:181, 234): lerp_, mul_ + addcmul_, addcdiv_ -- the operation order of optim_kernels.h
+    // the partials summed in tile order, then Adam with torch's defaults (pcn.py:181, 234)
     for (int q = tid; q < n.P; q += PCN_THREADS) {
         float g = a.part[q];
         for (int t = 1; t < a.ntiles; ++t) g += a.part[(size_t)t * n.P + q];
-        float m = a.exp_avg[q], v = a.exp_avg_sq[q];
-        m = fmaf(a.one_minus_b1, __fsub_rn(g, m), m);
-        v = __fadd_rn(__fmul_rn(v, a.b2), __fmul_rn(__fmul_rn(a.one_minus_b2, g), g));
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), a.bc2_sqrt), a.eps);
-        a.params[q] = __fadd_rn(a.params[q], __fmul_rn(a.neg_step_size, __fdiv_rn(m, denom)));
-        a.exp_avg[q] = m;
-        a.exp_avg_sq[q] = v;
+        pcn_adam(g, a.params[q], a.exp_avg[q], a.exp_avg_sq[q], a.one_minus_b1, a.b2, a.one_minus_b2, a.neg_step_size, a.bc2_sqrt,
+                 a.eps);
     }
 }
 

@@ -355,6 +355,101 @@ struct PpoLearner {
     float neg_step_size, bc2_sqrt;
 };
 
+// a single learner's record: the per-learner fields of its own argument block
+__device__ __forceinline__ PpoLearner ppo_own_learner(const PpoStepArgs& a) {
+    return PpoLearner{a.params, a.exp_avg, a.exp_avg_sq, a.table, a.idx, a.part, a.lpart, a.ticket, a.stats_out, a.table_rows,
+                      a.neg_step_size, a.bc2_sqrt};
+}
+
+// the table row of minibatch entry b, clamped into the table
+__device__ __forceinline__ int ppo_table_row(const int* __restrict__ idx, int b, int table_rows) {
+    return min(max(idx[b], 0), table_rows - 1);
+}
+
+// The value loss (mo_ppo.py:535-547, nl_mo_ppo.py:378-385) of row r of the tile, from the critic's output in L.out, L.ret and
+// L.oldv: writes the row's d loss / d value to L.dout and returns the row's sum over the objectives of max(unclipped, clipped)
+// squares (or of the unclipped square alone), 0 for a row past the minibatch.
+__device__ __forceinline__ float ppo_value_loss_row(PpoLds& L, const PpoStepArgs& a, int r, int valid) {
+    const int R = a.n.R;
+    float vsum = 0.0f;
+    const float gscale = __fmul_rn(__fmul_rn(0.5f, a.vf_coef), a.inv_MR);
+    for (int k = 0; k < R; ++k) {
+        const float v = L.out[r * R + k], ret = L.ret[r * R + k], ov = L.oldv[r * R + k];
+        float g = 0.0f;
+        if (r < valid) {
+            const float du = __fsub_rn(v, ret);
+            const float u = __fmul_rn(du, du);
+            g = __fmul_rn(2.0f, du);
+            float m = u;
+            if (a.clip_vloss) {
+                const float dv = __fsub_rn(v, ov);
+                const float vc = __fadd_rn(ov, fminf(fmaxf(dv, -a.clip_coef), a.clip_coef));
+                const float dc = __fsub_rn(vc, ret);
+                const float cl = __fmul_rn(dc, dc);
+                m = fmaxf(u, cl);
+                // inside the range both branches have the derivative 2 (v - ret); outside, the clipped branch has none
+                const bool inside = dv >= -a.clip_coef && dv <= a.clip_coef;
+                if (!inside) g = (u > cl) ? g : ((u == cl) ? du : 0.0f);
+            }
+            vsum = __fadd_rn(vsum, m);
+        }
+        L.dout[r * R + k] = __fmul_rn(g, gscale);
+    }
+    return vsum;
+}
+
+// The last workgroup's reduction: the gradient partials summed in tile order (four loads in flight, added in order) into tile
+// 0's slot, and clip_grad_norm_ (mo_ppo.py:553, nl_mo_ppo.py:392): the 2-norm of the per-tensor 2-norms; scale = max_norm /
+// (total + 1e-6) clamped to 1.  With `logstd`, tensor 0 is actor_logstd and takes the entropy's share, -ent_coef per entry.
+// Work-item 0 writes L.stat[2] = scale and L.stat[3] = total and returns the total norm (the others return 0); there is NO
+// barrier after that: the caller's work-item 0 writes its statistics and re-arms the ticket, then the barrier, then
+// ppo_adam_sweep.
+__device__ __forceinline__ float ppo_grad_clip(PpoLds& L, const PpoStepArgs& a, const PpoLearner& l, bool logstd) {
+    const PpoNet& n = a.n;
+    const int tid = (int)threadIdx.x;
+    for (int t = 0; t < n.ntensors; ++t) {
+        float sq = 0.0f;
+        for (int q = n.tstart[t] + tid; q < n.tstart[t + 1]; q += PPO_THREADS) {
+            float g = l.part[q];
+            int tl = 1;
+            for (; tl + 4 <= a.ntiles; tl += 4) {
+                const float g0 = l.part[(size_t)tl * n.P + q], g1 = l.part[(size_t)(tl + 1) * n.P + q];
+                const float g2 = l.part[(size_t)(tl + 2) * n.P + q], g3 = l.part[(size_t)(tl + 3) * n.P + q];
+                g = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(g, g0), g1), g2), g3);
+            }
+            for (; tl < a.ntiles; ++tl) g = __fadd_rn(g, l.part[(size_t)tl * n.P + q]);
+            if (logstd && t == 0) g = __fsub_rn(g, a.ent_coef);      // d(-ent_coef * entropy) / d logstd_k
+            l.part[q] = g;
+            sq = fmaf(g, g, sq);
+        }
+        L.w[t * PPO_THREADS + tid] = sq;
+    }
+    __syncthreads();
+    if (tid < n.ntensors) {
+        float s = 0.0f;
+        for (int i = 0; i < PPO_THREADS; ++i) s = __fadd_rn(s, L.w[tid * PPO_THREADS + i]);
+        L.red[tid] = __fsqrt_rn(s);
+    }
+    __syncthreads();
+    float total = 0.0f;
+    if (tid == 0) {
+        float s = 0.0f;
+        for (int t = 0; t < n.ntensors; ++t) s = fmaf(L.red[t], L.red[t], s);
+        total = __fsqrt_rn(s);
+        L.stat[2] = fminf(__fdiv_rn(a.max_grad_norm, __fadd_rn(total, 1e-6f)), 1.0f);
+        L.stat[3] = total;
+    }
+    return total;
+}
+
+// the clipped gradient (tile 0's slot times L.stat[2]) through torch _single_tensor_adam with eps 1e-5 (mo_ppo.py:331, 554)
+__device__ __forceinline__ void ppo_adam_sweep(const PpoLds& L, const PpoStepArgs& a, const PpoLearner& l) {
+    const float scale = L.stat[2];
+    for (int q = (int)threadIdx.x; q < a.n.P; q += PPO_THREADS)
+        pcn_adam(__fmul_rn(l.part[q], scale), l.params[q], l.exp_avg[q], l.exp_avg_sq[q], a.one_minus_b1, a.b2, a.one_minus_b2,
+                 l.neg_step_size, l.bc2_sqrt, a.eps);
+}
+
 // the body of ppo_step_kernel / ppo_pop_step_kernel: tile `tile` of learner `l`'s minibatch.  The shared fields are read from
 // `a`, the per-learner ones from `l` only.
 __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, const PpoLearner& l, int tile) {
@@ -369,7 +464,7 @@ __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, c
         const int r = o / n.D, d = o - r * n.D;
         float v = 0.0f;
         if (r < valid) {
-            const int row = min(max(l.idx[row0 + r], 0), l.table_rows - 1);
+            const int row = ppo_table_row(l.idx, row0 + r, l.table_rows);
             v = l.table[(size_t)row * a.row_w + d];
         }
         L.x[o] = v;
@@ -378,7 +473,7 @@ __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, c
         const int r = o / n.A, k = o - r * n.A;
         float v = 0.0f;
         if (r < valid) {
-            const int row = min(max(l.idx[row0 + r], 0), l.table_rows - 1);
+            const int row = ppo_table_row(l.idx, row0 + r, l.table_rows);
             v = l.table[(size_t)row * a.row_w + ao + k];
         }
         L.act[o] = v;
@@ -387,7 +482,7 @@ __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, c
         const int r = o / n.R, k = o - r * n.R;
         float ret = 0.0f, ov = 0.0f;
         if (r < valid) {
-            const int row = min(max(l.idx[row0 + r], 0), l.table_rows - 1);
+            const int row = ppo_table_row(l.idx, row0 + r, l.table_rows);
             ret = l.table[(size_t)row * a.row_w + ro + k];
             ov = l.table[(size_t)row * a.row_w + vo + k];
         }
@@ -397,7 +492,7 @@ __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, c
     if (tid < PPO_TB) {
         float lp = 0.0f, adv = 0.0f;
         if (tid < valid) {
-            const int row = min(max(l.idx[row0 + tid], 0), l.table_rows - 1);
+            const int row = ppo_table_row(l.idx, row0 + tid, l.table_rows);
             lp = l.table[(size_t)row * a.row_w + lo];
             adv = l.table[(size_t)row * a.row_w + adv_col];
         }
@@ -410,13 +505,13 @@ __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, c
     if (a.norm_adv) {
         float s = 0.0f;
         for (int b = tid; b < a.M; b += PPO_THREADS) {
-            const int row = min(max(l.idx[b], 0), l.table_rows - 1);
+            const int row = ppo_table_row(l.idx, b, l.table_rows);
             s = __fadd_rn(s, l.table[(size_t)row * a.row_w + adv_col]);
         }
         const float mean = __fdiv_rn(ppo_tree_sum(L.red, s), a.fM);
         float q = 0.0f;
         for (int b = tid; b < a.M; b += PPO_THREADS) {
-            const int row = min(max(l.idx[b], 0), l.table_rows - 1);
+            const int row = ppo_table_row(l.idx, b, l.table_rows);
             const float dlt = __fsub_rn(l.table[(size_t)row * a.row_w + adv_col], mean);
             q = fmaf(dlt, dlt, q);
         }
@@ -432,34 +527,7 @@ __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, c
 
     // ---- critic: forward, value loss (mo_ppo.py:535-547) and its gradient, backward
     ppo_mlp_forward(L, n, n.c, p, n.R);
-    if (tid < PPO_TB) {
-        const int r = tid;
-        float vsum = 0.0f;
-        const float gscale = __fmul_rn(__fmul_rn(0.5f, a.vf_coef), a.inv_MR);
-        for (int k = 0; k < n.R; ++k) {
-            const float v = L.out[r * n.R + k], ret = L.ret[r * n.R + k], ov = L.oldv[r * n.R + k];
-            float g = 0.0f;
-            if (r < valid) {
-                const float du = __fsub_rn(v, ret);
-                const float u = __fmul_rn(du, du);
-                g = __fmul_rn(2.0f, du);
-                float m = u;
-                if (a.clip_vloss) {
-                    const float dv = __fsub_rn(v, ov);
-                    const float vc = __fadd_rn(ov, fminf(fmaxf(dv, -a.clip_coef), a.clip_coef));
-                    const float dc = __fsub_rn(vc, ret);
-                    const float cl = __fmul_rn(dc, dc);
-                    m = fmaxf(u, cl);
-                    // inside the range both branches have the derivative 2 (v - ret); outside, the clipped branch has none
-                    const bool inside = dv >= -a.clip_coef && dv <= a.clip_coef;
-                    if (!inside) g = (u > cl) ? g : ((u == cl) ? du : 0.0f);
-                }
-                vsum = __fadd_rn(vsum, m);
-            }
-            L.dout[r * n.R + k] = __fmul_rn(g, gscale);
-        }
-        L.rs[r * PPO_NPART + 1] = vsum;
-    }
+    if (tid < PPO_TB) L.rs[tid * PPO_NPART + 1] = ppo_value_loss_row(L, a, tid, valid);
     __syncthreads();
     ppo_mlp_backward(L, n, n.c, p, part, n.R);
 
@@ -519,51 +587,9 @@ __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, c
     ppo_mlp_backward(L, n, n.a, p, part, n.A);
 
     // ---- the last workgroup to arrive owns the step
-    __threadfence();
-    __syncthreads();
+    if (!pcn_last_arrival(l.ticket, a.ntiles, L.last)) return;
+    const float total = ppo_grad_clip(L, a, l, true);
     if (tid == 0) {
-        const unsigned int prev = atomicAdd(l.ticket, 1u);
-        L.last = (prev + 1u == (unsigned int)a.ntiles) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!L.last) return;
-    __threadfence();
-
-    // the gradient: partials summed in tile order (four loads in flight, added in order), kept in tile 0's slot
-    float* grad = l.part;
-    for (int t = 0; t < n.ntensors; ++t) {
-        {
-            float sq = 0.0f;
-            for (int q = n.tstart[t] + tid; q < n.tstart[t + 1]; q += PPO_THREADS) {
-                float g = l.part[q];
-                int tl = 1;
-                for (; tl + 4 <= a.ntiles; tl += 4) {
-                    const float g0 = l.part[(size_t)tl * n.P + q], g1 = l.part[(size_t)(tl + 1) * n.P + q];
-                    const float g2 = l.part[(size_t)(tl + 2) * n.P + q], g3 = l.part[(size_t)(tl + 3) * n.P + q];
-                    g = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(g, g0), g1), g2), g3);
-                }
-                for (; tl < a.ntiles; ++tl) g = __fadd_rn(g, l.part[(size_t)tl * n.P + q]);
-                if (t == 0) g = __fsub_rn(g, a.ent_coef);      // d(-ent_coef * entropy) / d logstd_k
-                grad[q] = g;
-                sq = fmaf(g, g, sq);
-            }
-            L.w[t * PPO_THREADS + tid] = sq;
-        }
-    }
-    __syncthreads();
-    // clip_grad_norm_ (mo_ppo.py:553): the 2-norm of the per-tensor 2-norms; scale = max_norm / (total + 1e-6) clamped to 1
-    if (tid < n.ntensors) {
-        float s = 0.0f;
-        for (int i = 0; i < PPO_THREADS; ++i) s = __fadd_rn(s, L.w[tid * PPO_THREADS + i]);
-        L.red[tid] = __fsqrt_rn(s);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float s = 0.0f;
-        for (int t = 0; t < n.ntensors; ++t) s = fmaf(L.red[t], L.red[t], s);
-        const float total = __fsqrt_rn(s);
-        L.stat[2] = fminf(__fdiv_rn(a.max_grad_norm, __fadd_rn(total, 1e-6f)), 1.0f);
-        L.stat[3] = total;
         *l.ticket = 0u;                                        // re-armed for the next launch on the stream
         float ls[PPO_NPART];
         for (int i = 0; i < PPO_NPART; ++i) ls[i] = 0.0f;
@@ -582,26 +608,13 @@ __device__ __forceinline__ void ppo_step_tile(PpoLds& L, const PpoStepArgs& a, c
         l.stats_out[7] = total;
     }
     __syncthreads();
-    const float scale = L.stat[2];
-    // torch _single_tensor_adam with eps 1e-5 (mo_ppo.py:331, 554): lerp_, mul_ + addcmul_, addcdiv_
-    for (int q = tid; q < n.P; q += PPO_THREADS) {
-        const float g = __fmul_rn(grad[q], scale);
-        float m = l.exp_avg[q], v = l.exp_avg_sq[q];
-        m = fmaf(a.one_minus_b1, __fsub_rn(g, m), m);
-        v = __fadd_rn(__fmul_rn(v, a.b2), __fmul_rn(__fmul_rn(a.one_minus_b2, g), g));
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), l.bc2_sqrt), a.eps);
-        l.params[q] = __fadd_rn(l.params[q], __fmul_rn(l.neg_step_size, __fdiv_rn(m, denom)));
-        l.exp_avg[q] = m;
-        l.exp_avg_sq[q] = v;
-    }
+    ppo_adam_sweep(L, a, l);
 }
 
 
 static __global__ __launch_bounds__(PPO_THREADS) void ppo_step_kernel(PpoStepArgs a) {
     __shared__ PpoLds L;
-    const PpoLearner l{a.params, a.exp_avg, a.exp_avg_sq, a.table, a.idx, a.part, a.lpart, a.ticket, a.stats_out, a.table_rows,
-                       a.neg_step_size, a.bc2_sqrt};
-    ppo_step_tile(L, a, l, (int)blockIdx.x);
+    ppo_step_tile(L, a, ppo_own_learner(a), (int)blockIdx.x);
 }
 
 // blockIdx.y is the learner: its own parameters, moments, table, idx, partials, ticket, statistics row and Adam scalars.  The

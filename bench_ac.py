@@ -2,7 +2,7 @@
 continuous) on one MI355X.  bench.py stays the north-star (Envelope) line the driver runs; this script measures the
 widened rows with the same conventions:
 
-    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn|ppo|nlppo [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn|ppo|nlppo|eupg [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench_ac.py --workload morld --gpus N --pop 64      # the population's learners are independent units: pop / N per
                                                                 # GPU, no data-path collective ("replicas only", weak scaling)
@@ -40,6 +40,7 @@ SHAPES = {  # obs dim, action dim, objectives of the environments BASELINE.json 
     "ppo": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
     "pgmorl": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
     "nlppo": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (NL-MO-PPO, discrete: 6 actions)"),
+    "eupg": dict(D=1, Ad=2, R=2, env="fishwood-v0 (EUPG, discrete: 2 actions)"),
 }
 ARCH = [256, 256]
 B = 128
@@ -697,6 +698,99 @@ def bench_nlppo(a):
     print(json.dumps(out), file=RESULT_OUT, flush=True)
 
 
+def bench_eupg(a):
+    """EUPG (single_policy/esr/eupg.py): one ``EUPG.update()`` at the shapes of the reference's example (examples/eupg_fishwood.py:
+    obs 1, 2 actions, 2 objectives, net [50], an episode of 200 steps, the example's utility min(fish, wood // 2)) -- the scan
+    launch, the utility as torch ops on the device tensor, the step launch; next to it the same update as eager torch ops on the
+    same GPU (tests/eupg_oracle.py moved to the device: the reference's 200-iteration scan loop, Categorical, autograd, Adam).  The
+    episode is resident on the device in both legs.  The two legs alternate, ``--steps`` updates per timed window (a tenth of that
+    for the eager leg), five windows each; the figure is the median window.  The legs' first losses must agree to 1e-5."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ctypes as C
+
+    import eupg_oracle as eo
+    from morl_baselines_amd.native import load_library
+
+    lib, dev = load_library(), th.device("cuda", 0)
+    T, D, A, R, hidden, lr, gamma = 200, 1, 2, 2, [50], 1e-3, 0.99
+    loops = max(1, a.steps)
+
+    def utility(r, w=None):
+        return th.min(r[:, 0], r[:, 1] // 2)
+
+    th.manual_seed(0)
+    net = eo.PolicyNet(D, A, R, hidden)
+    g = th.Generator().manual_seed(1)
+    obs = th.randint(0, 2, (T, D), generator=g).int()                          # fishwood's state: at the river or in the woods
+    actions = th.randint(0, A, (T, 1), generator=g).int()
+    rewards = (th.rand(T, R, generator=g) < 0.3).float()                        # a fish or a piece of wood now and then
+    acc = th.cat([th.zeros(1, R), th.cumsum(rewards, 0)[:-1]])
+    to = lambda t: t.to(dev).contiguous()  # noqa: E731
+    obs_d, obs_f, acc_d, act_d, rew_d = to(obs), to(obs.float()), to(acc), to(actions), to(rewards)
+
+    h = C.c_void_p()
+    lib.check(lib.lib.morl_eupg_create(C.byref(h), D, A, R, 1, hidden[0], 0, T, 0))
+    stream = lib.stream_of(obs_d)
+    lib.check(lib.lib.morl_eupg_set_episode(h, obs_f.data_ptr(), acc_d.data_ptr(), act_d.data_ptr(), rew_d.data_ptr(), T, stream))
+    flat0 = th.cat([p.detach().reshape(-1) for p in net.parameters()]).to(dev)
+    state = dict(p=flat0.clone(), m=th.zeros_like(flat0), v=th.zeros_like(flat0), steps=0)
+    ret_d, loss_d = th.zeros(T, R, device=dev), th.zeros(1, device=dev)
+
+    def fused_update():
+        lib.check(lib.lib.morl_eupg_returns(h, gamma, ret_d.data_ptr(), stream))
+        u = utility(ret_d).contiguous()
+        lib.check(lib.lib.morl_eupg_update(h, state["p"].data_ptr(), state["m"].data_ptr(), state["v"].data_ptr(), u.data_ptr(), lr,
+                                           state["steps"], loss_d.data_ptr(), stream))
+        state["steps"] += 1
+        state["u"] = u                       # (alive until the launch has read it)
+
+    e_net = copy.deepcopy(net).to(dev)
+    opt = th.optim.Adam(e_net.parameters(), lr=lr)
+    eager = {}
+
+    def eager_update():
+        eager["loss"], eager["G"] = eo.update(e_net, opt, obs_d, acc_d, act_d, rew_d, gamma, utility)[:2]
+
+    # same inputs, same start: the first update of each leg must agree before anything is timed
+    fused_update()
+    eager_update()
+    th.cuda.synchronize()
+    loss_diff = float((loss_d[0] - eager["loss"]).abs() / eager["loss"].abs())
+    returns_equal = bool(th.equal(ret_d, eager["G"]))
+    if not loss_diff <= 1e-5:
+        raise RuntimeError(f"eupg: the fused and the eager leg's first losses differ by {loss_diff:.3e} relative (allowed 1e-5)")
+    for _ in range(max(1, a.warmup // 10)):
+        fused_update()
+        eager_update()
+    th.cuda.synchronize()
+    t = {"fused": [], "eager": []}
+    for _ in range(5):
+        for name, fn, reps in (("fused", fused_update, loops), ("eager", eager_update, max(1, loops // 10))):
+            th.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            th.cuda.synchronize()
+            t[name].append((time.perf_counter() - t0) * 1e3 / reps)
+    lib.lib.morl_eupg_destroy(h)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    out = {"metric": "EUPG updates/sec (one episode of 200 steps per update())", "value": 1e3 / med["fused"], "unit": "updates/s",
+           "n_gpus": 1, "steps": loops, "warmup": a.warmup, "ms_per_step": med["fused"], "higher_is_better": True, "vs_baseline": None,
+           "dtype": "f32", "data": "synthetic",
+           "config": {"workload": "EUPG.update() at the shapes of examples/eupg_fishwood.py: obs 1, 2 actions, 2 objectives, net [50], an "
+                                  "episode of 200 steps, utility min(fish, wood // 2); the scan launch, the utility in torch on the "
+                                  "device, the step launch; comparison: the same update as eager torch ops on the same GPU"},
+           "shape": dict(obs_dim=D, n_actions=A, reward_dim=R, hidden=hidden, episode_rows=T, tiles=(T + 15) // 16),
+           "fused_us_per_update": med["fused"] * 1e3, "eager_torch_us_per_update": med["eager"] * 1e3,
+           "eager_over_fused": med["eager"] / med["fused"], "fused_windows_ms": t["fused"], "eager_windows_ms": t["eager"],
+           "fused_slowest_below_eager_fastest": bool(max(t["fused"]) < min(t["eager"])),
+           "first_loss_rel_diff": loss_diff, "returns_bit_equal": returns_equal,
+           "loops_per_window": {"fused": loops, "eager": max(1, loops // 10)},
+           "roofline": {"bound": "latency", "kernel": "eupg_step_kernel", "achieved": None, "peak": None, "unit": None, "frac": None,
+                        "traffic": None, "note": "13 tiles of 16 rows, ~0.1 MFLOP and < 100 KB per update: launch- and dependency-latency-bound"}}
+    print(json.dumps(out), file=RESULT_OUT, flush=True)
+
+
 def bench_pgmorl(a):
     """PGMORL's population (multi_policy/pgmorl/pgmorl.py, ``pop_size`` MOPPO learners) at the ``ppo`` row's shapes: every learner
     has its own parameters, rollout and shuffles.  Three pairs, each timed in the same process in interleaved windows (five per leg,
@@ -961,6 +1055,8 @@ def main():
         return bench_ppo(a)
     if a.workload == "nlppo":
         return bench_nlppo(a)
+    if a.workload == "eupg":
+        return bench_eupg(a)
     if a.workload == "pgmorl":
         return bench_pgmorl(a)
     from morl_baselines_amd.ac_engine import ALGO_CAPQL, ALGO_MOSAC, ALGO_TD3, ACEngine

@@ -961,6 +961,53 @@ int morl_nlppo_update_n(morl_nlppo_ctx* ctx, float* params, float* exp_avg, floa
 int morl_nlppo_forward(morl_nlppo_ctx* ctx, const float* params, const float* obs, const float* acc_reward, const float* pref,
                        int rows, int value_only, float* logp_out, float* value_out, void* stream);
 
+/* ================================================================================================
+ * Expected Utility Policy Gradient (single_policy/esr/eupg.py), the reference's ESR learner
+ *   PolicyNet (:22-75):     input = obs | accrued reward [R];  input -> hidden (Tanh) -> z [A];  p_j = sigmoid(z_j) / sum_j
+ *                           sigmoid(z_j), each row normalised on its own (the reference's batch-wide divisor cancels in
+ *                           Categorical's own normalisation)
+ *   update() (:227-251):    G_t = gamma * G_{t+1} + r_t;  u = scalarization(G) (the caller's);  loss = -mean_t(log(clamp(p_t[a_t],
+ *                           eps, 1 - eps)) * u_t) with eps = 2^-23: a row whose p_t[a_t] leaves [eps, 1 - eps] contributes no
+ *                           gradient;  Adam with torch's defaults (eps 1e-8), no gradient clipping -- one launch for the scan,
+ *                           one for forward, loss, backward and the optimiser step
+ * Parameters are one flat fp32 vector in the order of PolicyNet.parameters():
+ *   net.0.weight [H0][D_in], net.0.bias, (net.2.weight [H1][H0], net.2.bias,) head weight [A][H], head bias;  D_in = obs_dim +
+ *   reward_dim.
+ * Limits (MORL_ERR_ARG otherwise): obs_dim >= 1, D_in <= 128, n_actions 2..32, reward_dim 1..8, one or two hidden layers of ANY
+ * width 1..128.  A row whose sigmoids are all exactly 0 is not defined here (the reference yields NaN).
+ * The entries take scalars and pointers only; every pointer is device memory; nothing synchronises the host.  A refused call
+ * launches nothing and leaves the context usable.
+ * ================================================================================================ */
+typedef struct morl_eupg_ctx morl_eupg_ctx;
+
+/* -1 (and morl_last_error) for a shape outside the limits; hidden1 is ignored when n_hidden == 1 */
+int64_t morl_eupg_param_count(int obs_dim, int n_actions, int reward_dim, int n_hidden, int hidden0, int hidden1);
+/* max_rows: longest episode of morl_eupg_set_episode (0: 1024);  max_workgroups: cap of the step launch's grid (0: 64, at most
+ * 1024) -- with fewer workgroups than 16-row tiles a workgroup owns several tiles and adds them in tile order */
+int morl_eupg_create(morl_eupg_ctx** out, int obs_dim, int n_actions, int reward_dim, int n_hidden, int hidden0, int hidden1,
+                     int max_rows, int max_workgroups);
+int morl_eupg_destroy(morl_eupg_ctx* ctx);
+/* Replace the context's episode with T steps: obs [T][obs_dim] (as update() sees them: the reference's buffer holds them as
+ * int32, the caller truncates), acc_rewards [T][R], actions [T] (int32 indices; one outside [0, n_actions) is clamped when the step
+ * gathers it), rewards [T][R].  The context keeps its own table, one row per step: input [D_in] | action. */
+int morl_eupg_set_episode(morl_eupg_ctx* ctx, const float* obs, const float* acc_rewards, const int32_t* actions, const float* rewards,
+                          int T, void* stream);
+/* The reverse discounted scan over the episode's rewards: out [T][R], G_t = gamma * G_{t+1} + r_t in fp32 (a multiply, then an
+ * add; gamma rounded to float once): bit for bit what _forward_cumulative_rewards computes. */
+int morl_eupg_returns(morl_eupg_ctx* ctx, double gamma, float* out, void* stream);
+/* One optimiser step on the whole episode, one launch.  scalarized_values [T]: the utility of each row's return; Adam with betas
+ * 0.9 / 0.999 and eps 1e-8, steps_done = steps taken before this call; loss_out [1].  Results are bit-identical run to run for one
+ * max_workgroups; another grid adds the partials in another order. */
+int morl_eupg_update(morl_eupg_ctx* ctx, float* params, float* exp_avg, float* exp_avg_sq, const float* scalarized_values, double lr,
+                     int steps_done, float* loss_out, void* stream);
+/* probs_out [T][n_actions]: the probabilities the last morl_eupg_update formed for the episode's rows (at the parameters BEFORE
+ * that step).  MORL_ERR_STATE before the first step on an episode. */
+int morl_eupg_step_probs(morl_eupg_ctx* ctx, float* probs_out, void* stream);
+/* No-grad forward on obs [rows][obs_dim], acc_reward [rows][R]: probs_out [rows][n_actions], computed as a step computes them
+ * (the same bits while the parameters are unchanged).  Sampling is the caller's. */
+int morl_eupg_forward(morl_eupg_ctx* ctx, const float* params, const float* obs, const float* acc_reward, int rows, float* probs_out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("NLMOPPO", "Agent"):
         from . import nl_mo_ppo
         return getattr(nl_mo_ppo, name)
+    if name == "EUPG":
+        from .eupg import EUPG
+        return EUPG
     if name == "PGMORL":
         from .pgmorl import PGMORL
         return PGMORL

@@ -43,6 +43,13 @@ except Exception:  # pragma: no cover - exercised on boxes without the reference
             rets = [_eval_mo(self, eval_env, weights, scalarization) for _ in range(num_episodes)]
             return tuple(np.mean([r[k] for r in rets], axis=0) for k in range(4))
 
+        def policy_eval_esr(self, eval_env, scalarization, weights: Optional[np.ndarray] = None, log: bool = False):
+            """One episode of a policy conditioned on the accrued reward (``morl_algorithm.py:127-159`` ->
+            ``evaluation.py:70-115``): scalarised return, scalarised discounted return, return, discounted return."""
+            if log:
+                raise ImportError("wandb logging needs the reference package (morl_baselines) and wandb installed")
+            return _eval_mo_reward_conditioned(self, eval_env, scalarization, weights)
+
         def get_policy_net(self):
             pass
 
@@ -116,6 +123,24 @@ except Exception:  # pragma: no cover - exercised on boxes without the reference
         if w is None:
             return float(vec_return), float(disc_vec_return), vec_return, disc_vec_return
         return scalarization(w, vec_return), scalarization(w, disc_vec_return), vec_return, disc_vec_return
+
+
+    def _eval_mo_reward_conditioned(agent, env, scalarization=np.dot, w=None):
+        """One episode of an ESR agent, which is handed the DISCOUNTED accrued reward (``common/evaluation.py:70-115``)."""
+        obs, _ = env.reset()
+        done = False
+        R = env.unwrapped.reward_space.shape[0]
+        vec_return, disc_vec_return = np.zeros(R), np.zeros(R)
+        gamma = 1.0
+        while not done:
+            obs, r, terminated, truncated, _ = env.step(agent.eval(obs, disc_vec_return))
+            done = terminated or truncated
+            vec_return += r
+            disc_vec_return += gamma * r
+            gamma *= agent.gamma
+        if w is None:
+            return scalarization(vec_return), scalarization(disc_vec_return), vec_return, disc_vec_return
+        return scalarization(vec_return, w), scalarization(disc_vec_return, w), vec_return, disc_vec_return
 
 
 def reference_method(module: str, cls: str, name: str):

@@ -2777,3 +2777,167 @@ extern "C" int morl_nlppo_forward(morl_nlppo_ctx* c, const float* params, const 
     LAUNCH_CHECK("nlppo_forward");
     return MORL_OK;
 }
+
+
+// =====================================================================================================================
+// Expected Utility Policy Gradient (include/morl_hip.h, "Expected Utility Policy Gradient")
+// =====================================================================================================================
+#include "eupg_kernels.h"
+
+constexpr int EUPG_DEFAULT_ROWS = 1024, EUPG_DEFAULT_WORKGROUPS = 64, EUPG_MAX_WORKGROUPS = 1024;
+
+// Not a PpoWork: the episode is one batch with no minibatch index, no dones and no GAE state, the partials are per workgroup
+// (twice) and every buffer has its final size from morl_eupg_create on.
+struct morl_eupg_ctx {
+    PpoNet n{};                    // n.D = obs_dim + reward_dim; the policy is n.a
+    int obs_dim = 0, max_rows = 0, max_wg = 0, row_w = 0;
+    int T = 0;                     // rows of the episode in the table, 0: none
+    float* table = nullptr;        // [max_rows][row_w]
+    float* rewards = nullptr;      // [max_rows][R]
+    float* probs = nullptr;        // [max_rows][A]
+    float* part = nullptr;         // [2][max_wg][P]
+    float* lpart = nullptr;        // [max_wg]
+    unsigned int* ticket = nullptr;
+    int have_probs = 0;
+};
+
+// the flat vector in the order of PolicyNet.parameters(): net.0.weight [H0][D_in], net.0.bias, (net.2.*), head weight, head bias
+static int eupg_fill(PpoNet& n, int obs_dim, int A, int R, int nh, int h0, int h1) {
+    if (obs_dim < 1) return fail(MORL_ERR_ARG, "EUPG: obs_dim %d is not at least 1", obs_dim);
+    if (R < 1 || R > PPO_MAX_R) return fail(MORL_ERR_ARG, "EUPG: reward_dim %d outside 1..%d", R, PPO_MAX_R);
+    if ((int64_t)obs_dim + R > PPO_MAX_D) return fail(MORL_ERR_ARG, "EUPG: input width obs_dim %d + reward_dim %d exceeds %d", obs_dim, R, PPO_MAX_D);
+    if (A < 2 || A > PPO_MAX_A) return fail(MORL_ERR_ARG, "EUPG: n_actions %d outside 2..%d", A, PPO_MAX_A);
+    if (nh < 1 || nh > 2) return fail(MORL_ERR_ARG, "EUPG: n_hidden %d is not 1 or 2 hidden layers", nh);
+    const int hs[2] = {h0, h1};
+    for (int l = 0; l < nh; ++l)
+        if (hs[l] < 1 || hs[l] > PPO_MAX_H) return fail(MORL_ERR_ARG, "EUPG: hidden width %d (layer %d) outside 1..%d", hs[l], l, PPO_MAX_H);
+    n = PpoNet{};
+    n.D = obs_dim + R; n.A = A; n.R = R; n.nh = nh; n.H1 = h0; n.H2 = (nh == 2) ? h1 : h0;
+    int o = 0, t = 0;
+    auto take = [&](int count) { const int at = o; n.tstart[t++] = o; o += count; return at; };
+    PpoMlp& m = n.a;
+    m.oW0 = take(n.H1 * n.D);
+    m.ob0 = take(n.H1);
+    if (nh == 2) {
+        m.oW1 = take(n.H2 * n.H1);
+        m.ob1 = take(n.H2);
+    }
+    m.oWo = take(A * n.H2);
+    m.obo = take(A);
+    n.P = o;
+    n.ntensors = t;
+    for (int i = t; i <= PPO_MAX_TENSORS; ++i) n.tstart[i] = o;
+    return MORL_OK;
+}
+
+extern "C" int64_t morl_eupg_param_count(int obs_dim, int n_actions, int reward_dim, int n_hidden, int hidden0, int hidden1) {
+    PpoNet n{};
+    return eupg_fill(n, obs_dim, n_actions, reward_dim, n_hidden, hidden0, hidden1) ? -1 : n.P;
+}
+
+extern "C" int morl_eupg_destroy(morl_eupg_ctx* c) {
+    if (!c) return MORL_OK;
+    for (void* p : {(void*)c->table, (void*)c->rewards, (void*)c->probs, (void*)c->part, (void*)c->lpart, (void*)c->ticket})
+        if (p) (void)hipFree(p);
+    delete c;
+    return MORL_OK;
+}
+
+extern "C" int morl_eupg_create(morl_eupg_ctx** out, int obs_dim, int n_actions, int reward_dim, int n_hidden, int hidden0,
+                                int hidden1, int max_rows, int max_workgroups) {
+    if (!out) return fail(MORL_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    PpoNet n{};
+    int rc = eupg_fill(n, obs_dim, n_actions, reward_dim, n_hidden, hidden0, hidden1);
+    if (rc) return rc;
+    if (max_rows == 0) max_rows = EUPG_DEFAULT_ROWS;
+    if (max_workgroups == 0) max_workgroups = EUPG_DEFAULT_WORKGROUPS;
+    if (max_rows < 1 || max_rows > (1 << 20)) return fail(MORL_ERR_ARG, "EUPG: max_rows %d outside 1..%d (0: %d)", max_rows, 1 << 20, EUPG_DEFAULT_ROWS);
+    if (max_workgroups < 1 || max_workgroups > EUPG_MAX_WORKGROUPS)
+        return fail(MORL_ERR_ARG, "EUPG: max_workgroups %d outside 1..%d (0: %d)", max_workgroups, EUPG_MAX_WORKGROUPS, EUPG_DEFAULT_WORKGROUPS);
+    morl_eupg_ctx* c = new (std::nothrow) morl_eupg_ctx();
+    if (!c) return fail(MORL_ERR_ALLOC, "out of host memory");
+    c->n = n;
+    c->obs_dim = obs_dim;
+    c->max_rows = max_rows;
+    c->max_wg = std::min(max_workgroups, (max_rows + PPO_TB - 1) / PPO_TB);
+    c->row_w = n.D + 1;
+    if ((rc = dmalloc((void**)&c->table, (size_t)max_rows * c->row_w * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->rewards, (size_t)max_rows * n.R * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->probs, (size_t)max_rows * n.A * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->part, (size_t)2 * c->max_wg * n.P * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->lpart, (size_t)c->max_wg * sizeof(float))) ||
+        (rc = dmalloc((void**)&c->ticket, sizeof(unsigned int)))) {
+        morl_eupg_destroy(c);
+        return rc;
+    }
+    if (hipMemset(c->ticket, 0, sizeof(unsigned int)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        morl_eupg_destroy(c);
+        return fail(MORL_ERR_HIP, "EUPG: workspace init failed");
+    }
+    *out = c;
+    return MORL_OK;
+}
+
+extern "C" int morl_eupg_set_episode(morl_eupg_ctx* c, const float* obs, const float* acc_rewards, const int32_t* actions,
+                                     const float* rewards, int T, void* stream) {
+    if (!c || !obs || !acc_rewards || !actions || !rewards) return fail(MORL_ERR_ARG, "NULL argument");
+    if (T < 1 || T > c->max_rows) return fail(MORL_ERR_ARG, "EUPG: episode of %d steps outside 1..max_rows %d", T, c->max_rows);
+    HIP_TRY(hipMemcpyAsync(c->rewards, rewards, (size_t)T * c->n.R * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    const int64_t total = (int64_t)T * c->row_w;
+    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 1024);
+    hipLaunchKernelGGL(eupg_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c->obs_dim, c->n.R, c->row_w, T, obs,
+                       acc_rewards, (const int*)actions, c->table);
+    LAUNCH_CHECK("eupg_pack");
+    c->T = T;
+    c->have_probs = 0;
+    return MORL_OK;
+}
+
+extern "C" int morl_eupg_returns(morl_eupg_ctx* c, double gamma, float* out, void* stream) {
+    if (!c || !out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (c->T < 1) return fail(MORL_ERR_STATE, "EUPG: no episode (morl_eupg_set_episode)");
+    hipLaunchKernelGGL(eupg_return_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, c->T, c->n.R, c->rewards, (float)gamma, out);
+    LAUNCH_CHECK("eupg_return");
+    return MORL_OK;
+}
+
+extern "C" int morl_eupg_update(morl_eupg_ctx* c, float* params, float* exp_avg, float* exp_avg_sq, const float* scalarized_values,
+                                double lr, int steps_done, float* loss_out, void* stream) {
+    if (!c || !params || !exp_avg || !exp_avg_sq || !scalarized_values || !loss_out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (c->T < 1) return fail(MORL_ERR_STATE, "EUPG: no episode (morl_eupg_set_episode)");
+    if (steps_done < 0) return fail(MORL_ERR_ARG, "steps_done %d", steps_done);
+    EupgStepArgs a{};
+    a.n = c->n;
+    a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
+    a.table = c->table; a.u = scalarized_values;
+    a.row_w = c->row_w; a.T = c->T;
+    a.ntiles = (c->T + PPO_TB - 1) / PPO_TB;
+    a.nwg = std::min(a.ntiles, c->max_wg);
+    a.part = c->part; a.tpart = c->part + (size_t)c->max_wg * c->n.P;
+    a.lpart = c->lpart; a.probs = c->probs; a.ticket = c->ticket; a.loss_out = loss_out;
+    a.fT = (float)c->T;
+    a.one_minus_b1 = (float)(1.0 - 0.9); a.b2 = (float)0.999; a.one_minus_b2 = (float)(1.0 - 0.999); a.eps = 1e-8f;
+    ppo_adam_bias(lr, steps_done + 1, a.neg_step_size, a.bc2_sqrt);
+    hipLaunchKernelGGL(eupg_step_kernel, dim3(a.nwg), dim3(PPO_THREADS), 0, (hipStream_t)stream, a);
+    LAUNCH_CHECK("eupg_step");
+    c->have_probs = 1;
+    return MORL_OK;
+}
+
+extern "C" int morl_eupg_step_probs(morl_eupg_ctx* c, float* probs_out, void* stream) {
+    if (!c || !probs_out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (!c->have_probs) return fail(MORL_ERR_STATE, "EUPG: no step on this episode yet (morl_eupg_update)");
+    HIP_TRY(hipMemcpyAsync(probs_out, c->probs, (size_t)c->T * c->n.A * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
+    return MORL_OK;
+}
+
+extern "C" int morl_eupg_forward(morl_eupg_ctx* c, const float* params, const float* obs, const float* acc_reward, int rows,
+                                 float* probs_out, void* stream) {
+    if (!c || !params || !obs || !acc_reward || !probs_out) return fail(MORL_ERR_ARG, "NULL argument");
+    if (rows < 1) return fail(MORL_ERR_ARG, "EUPG: rows = %d", rows);
+    hipLaunchKernelGGL(eupg_forward_kernel, dim3((rows + PPO_TB - 1) / PPO_TB), dim3(PPO_THREADS), 0, (hipStream_t)stream, c->n,
+                       c->obs_dim, params, obs, acc_reward, rows, probs_out);
+    LAUNCH_CHECK("eupg_forward");
+    return MORL_OK;
+}

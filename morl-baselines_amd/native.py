@@ -285,6 +285,14 @@ _SIGNATURES = {
     "morl_nlppo_update_n": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int] +
                             [C.c_double] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "morl_nlppo_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "morl_eupg_param_count": (C.c_int64, [C.c_int] * 6),
+    "morl_eupg_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 8),
+    "morl_eupg_destroy": (C.c_int, [C.c_void_p]),
+    "morl_eupg_set_episode": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p]),
+    "morl_eupg_returns": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "morl_eupg_update": (C.c_int, [C.c_void_p] * 5 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
+    "morl_eupg_step_probs": (C.c_int, [C.c_void_p] * 3),
+    "morl_eupg_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

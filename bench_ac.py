@@ -2,7 +2,7 @@
 continuous) on one MI355X.  bench.py stays the north-star (Envelope) line the driver runs; this script measures the
 widened rows with the same conventions:
 
-    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn|ppo|nlppo|eupg [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn|lcn|ppo|nlppo|eupg [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench_ac.py --workload morld --gpus N --pop 64      # the population's learners are independent units: pop / N per
                                                                 # GPU, no data-path collective ("replicas only", weak scaling)
@@ -37,6 +37,7 @@ SHAPES = {  # obs dim, action dim, objectives of the environments BASELINE.json 
     "gpi": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (GPI-PD, discrete: 6 actions)"),
     "ens": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (GPI-PD Dyna model: one-hot action in, next-obs delta + reward out)"),
     "pcn": dict(D=9, Ad=4, R=2, env="treasure-line (discrete head) / mo-hopper-v4 shapes 11-3-3 (continuous head)"),
+    "lcn": dict(D=9, Ad=4, R=3, env="heaps of 500 / 2048 episode returns in 3 / 8 objectives (LCN's selection)"),
     "ppo": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
     "pgmorl": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
     "nlppo": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (NL-MO-PPO, discrete: 6 actions)"),
@@ -439,6 +440,120 @@ def bench_pcn(a):
            "heads": heads,
            "roofline": {"bound": "latency", "kernel": "pcn_step_kernel", "achieved": None, "peak": None, "unit": None, "frac": None,
                         "traffic": None, "note": "~10 MFLOP and < 1 MB per update: launch- and dependency-latency-bound"}}
+    print(json.dumps(out), file=RESULT_OUT, flush=True)
+
+
+def bench_lcn(a):
+    """LCN (multi_policy/lcn/lcn.py): the scoring of ``_nlargest`` (lcn.py:226-252) as ONE ``morl_lcn_select`` launch, at LCN's
+    default heap (N = 500, R = 3) and at the kernel's limit (N = 2048, R = 8): timed end to end as ``LCN._select`` uses it
+    (upload of the returns and the crowding flags, the launch, one read-back) and as the launch alone; next to it the numpy
+    selection of tests/lcn_oracle.py (the reference's lines, crowding distance excluded on both sides) on this machine's host,
+    and for scale the 100 ``update()`` calls between two selections (batch 32, hidden 64) as one ``morl_pcn_update_n`` call.
+    The legs alternate, ``--steps`` calls per timed window, five windows each; the figure is the median window."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import ctypes as C
+
+    import lcn_cases as lc
+    import lcn_oracle as lo
+    import pcn_oracle as po
+    from morl_baselines_amd.native import load_library
+
+    lib, dev = load_library(), th.device("cuda", 0)
+    loops = max(1, a.steps)
+    L = lib.lib.morl_lcn_select
+
+    # -- the update loop of one iteration (lcn.py:449-455): 100 updates, batch 32, hidden 64, treasure-line shapes -------------------
+    n_upd, Bu, H, lr, (D, R, A) = 100, 32, 64, 1e-2, (9, 2, 4)
+    rng = np.random.default_rng(0)
+    rows = 10000                                        # ~500 stored episodes of ~20 transitions (max_buffer_size = 500)
+    table = rng.standard_normal((rows, D + 1 + R + 1)).astype(np.float32)
+    table[:, D] = rng.integers(0, A, rows)
+    table[:, -1] = rng.integers(1, 20, rows)
+    idx_d = th.tensor(rng.integers(0, rows, (n_upd, Bu)).astype(np.int32)).to(dev)
+    table_d = th.tensor(table).to(dev)
+    scaling_d = th.tensor(np.linspace(0.1, 0.02, R + 1).astype(np.float32)).to(dev)
+    th.manual_seed(0)
+    flat0 = th.cat([p.reshape(-1) for p in po.init_params(D, R, A, H)]).to(dev)
+    h = C.c_void_p()
+    lib.check(lib.lib.morl_pcn_create(C.byref(h), D, R, A, H, 0, Bu))
+    lib.check(lib.lib.morl_pcn_set_table(h, table_d.data_ptr(), rows, lib.stream_of(table_d)))
+    st = dict(p=flat0.clone(), m=th.zeros_like(flat0), v=th.zeros_like(flat0), steps=0)
+    loss_d, ent_d, pred_d = th.zeros(n_upd, device=dev), th.zeros(n_upd, device=dev), th.zeros(Bu, A, device=dev)
+
+    def update_loop():
+        lib.check(lib.lib.morl_pcn_update_n(h, st["p"].data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), scaling_d.data_ptr(), n_upd,
+                                            idx_d.data_ptr(), Bu, lr, st["steps"], loss_d.data_ptr(), ent_d.data_ptr(),
+                                            pred_d.data_ptr(), lib.stream_of(loss_d)))
+        st["steps"] += n_upd
+        return loss_d.cpu(), ent_d.cpu()                # train() reads both back every iteration
+
+    shapes = {}
+    for tag, (N, Rs, mode, lam) in (("n500_r3", (500, 3, 1, 0.0)), ("n2048_r8", (2048, 8, 1, 0.0)),
+                                    ("n500_r3_lambda", (500, 3, 2, 0.5))):
+        returns = lc.select_returns(N, Rs, "cont", seed=N + Rs)
+        want_l2, want_mask, crowded = lo.score(returns, 0.2, mode, lam)
+        ret_d, sma_d = th.tensor(returns).to(dev), th.tensor(crowded).to(dev)
+        l2_d, nd_d = th.empty(N, device=dev), th.empty(N, dtype=th.uint8, device=dev)
+
+        def launch_only():
+            lib.check(L(ret_d.data_ptr(), N, Rs, mode, lam, sma_d.data_ptr(), l2_d.data_ptr(), nd_d.data_ptr(), lib.stream_of(nd_d)))
+
+        def end_to_end():
+            r, s = th.from_numpy(returns).to(dev), th.from_numpy(crowded).to(dev)
+            l2, nd = th.empty(N, device=dev), th.empty(N, dtype=th.uint8, device=dev)
+            lib.check(L(r.data_ptr(), N, Rs, mode, lam, s.data_ptr(), l2.data_ptr(), nd.data_ptr(), lib.stream_of(nd)))
+            out = th.cat((l2.view(th.uint8), nd)).cpu().numpy()
+            return out[:4 * N].view(np.float32), out[4 * N:]
+
+        def numpy_leg():
+            return lo.score(returns, 0.2, mode, lam, crowded=crowded)
+
+        # same inputs: the device's l2 is numpy's, bit for bit, before anything is timed
+        got_l2, got_nd = end_to_end()
+        exact = bool(np.array_equal(got_l2.view(np.uint32), want_l2.view(np.uint32)) and np.array_equal(got_nd.astype(bool), want_mask))
+        if not exact:
+            raise SystemExit(f"bench_ac lcn {tag}: the device selection differs from numpy's")
+        for _ in range(max(1, a.warmup)):
+            launch_only()
+            end_to_end()
+        numpy_leg()
+        update_loop()
+        th.cuda.synchronize()
+        t = {"launch": [], "end_to_end": [], "numpy": [], "update_loop": []}
+        for _ in range(5):
+            for name, fn, reps, sync in (("launch", launch_only, loops, True), ("end_to_end", end_to_end, loops, False),
+                                         ("numpy", numpy_leg, max(1, loops // 10), False),
+                                         ("update_loop", update_loop, max(1, loops // 10), False)):
+                th.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    fn()
+                if sync:
+                    th.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) * 1e6 / reps)
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        shapes[tag] = {"shape": dict(N=N, R=Rs, mode=mode, lcn_lambda=lam, front=int(want_mask.sum()), crowded=int(crowded.sum())),
+                       "bit_identical_to_numpy": exact,
+                       "device_end_to_end_us": med["end_to_end"], "device_launch_only_us": med["launch"],
+                       "numpy_host_us": med["numpy"], "numpy_over_device_end_to_end": med["numpy"] / med["end_to_end"],
+                       "update_loop_100x_batch32_us": med["update_loop"],
+                       "windows_us": t, "calls_per_window": {"launch": loops, "end_to_end": loops, "numpy": max(1, loops // 10),
+                                                            "update_loop": max(1, loops // 10)}}
+    lib.lib.morl_pcn_destroy(h)
+    d = shapes["n500_r3"]
+    out = {"metric": "LCN selections/sec (morl_lcn_select end to end: upload, one launch, read-back; N = 500, R = 3)",
+           "value": 1e6 / d["device_end_to_end_us"], "unit": "selections/s", "n_gpus": 1, "steps": loops, "warmup": a.warmup,
+           "ms_per_step": d["device_end_to_end_us"] / 1e3, "higher_is_better": True, "vs_baseline": None, "dtype": "f32",
+           "data": "synthetic",
+           "config": {"workload": "LCN._nlargest's scoring (lcn.py:226-252) at the default heap of 500 episodes and at the kernel's "
+                                  "limit; comparison: the same lines in numpy on this host (tests/lcn_oracle.py), and the 100-update "
+                                  "loop of one training iteration (morl_pcn_update_n, batch 32, hidden 64, losses and entropies read "
+                                  "back) for scale"},
+           "shapes": shapes,
+           "roofline": {"bound": "latency", "kernel": "lcn_select_kernel", "achieved": None, "peak": None, "unit": None, "frac": None,
+                        "traffic": None, "note": "one workgroup, N^2 pair tests on LDS broadcasts; the end-to-end call is two "
+                                                 "uploads, a launch and a blocking read-back"}}
     print(json.dumps(out), file=RESULT_OUT, flush=True)
 
 
@@ -1051,6 +1166,8 @@ def main():
         return bench_ens(a)
     if a.workload == "pcn":
         return bench_pcn(a)
+    if a.workload == "lcn":
+        return bench_lcn(a)
     if a.workload == "ppo":
         return bench_ppo(a)
     if a.workload == "nlppo":

@@ -440,6 +440,22 @@ int morl_polyak(const float* src, float* dst, float tau, int64_t n, void* stream
  * early exits, i.e. execute all N^2 pair tests -- same mask. */
 int morl_pareto_mask(const double* points, int N, int R, int remove_duplicates, uint8_t* mask_out, void* stream);
 
+/* ---- LCN._nlargest's scoring: multi_policy/lcn/lcn.py:221-252 (and PCN's, pcn.py:250-279, as mode 0) ------------------
+ * returns: device float32 [N][R], the episode returns in heap order, finite.  mode 0: Pareto dominance on the raw returns;
+ * 1: strict Lorenz dominance (distance_ref="nondominated"); 2: lambda-Lorenz ("lambda_lorenz"; lcn_lambda is the reference's
+ * Python float: the kernel multiplies by float(lcn_lambda) and float(1.0 - lcn_lambda) as numpy does, so it is passed as a
+ * double; ignored in modes 0 and 1).  crowded: device uint8 [N], 1 where crowding_distance(returns) <= threshold (the host's
+ * `sma`: the reference forms it with an unstable argsort whose tie order no kernel can restate).
+ * nd_out [N]: get_non_dominated_inds of the (Lorenz / lambda-Lorenz) rows.  l2_out [N]: minus the distance to the closest
+ * front point, minus 1e-5 for everything but the first occurrence of a front point, doubled where crowded -- float32,
+ * bit for bit what numpy computes (every product, difference and sum rounded on its own, numpy's summation order, a
+ * correctly rounded square root).  crowded and l2_out may be NULL together: only nd_out is written.
+ * One launch of one workgroup that holds both row sets in LDS, nothing synchronises the host; N is 1..MORL_LCN_MAX_N,
+ * R 1..MORL_MAX_OBJ, anything else is refused. */
+#define MORL_LCN_MAX_N 2048
+int morl_lcn_select(const float* returns, int N, int R, int mode, double lcn_lambda, const uint8_t* crowded, float* l2_out,
+                    uint8_t* nd_out, void* stream);
+
 /* ---- front metrics: common/performance_indicators.py -------------------------------------------------------------
  * hypervolume(ref_point, points) (:15-25; the reference negates both and calls pymoo's minimisation HV -- the quantity
  * is the volume dominated by the points and dominating ref_point) and expected_utility(front, weights_set) (:71-91,

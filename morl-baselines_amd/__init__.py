@@ -15,6 +15,9 @@ def __getattr__(name):
     if name == "PCN":
         from .pcn import PCN
         return PCN
+    if name == "LCN":
+        from .lcn import LCN
+        return LCN
     if name in ("MOPPO", "MOPPONet"):
         from . import mo_ppo
         return getattr(mo_ppo, name)

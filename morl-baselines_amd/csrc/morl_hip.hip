@@ -31,6 +31,7 @@
 #include "optim_kernels.h"
 #include "replay_kernels.h"
 #include "pareto_kernels.h"
+#include "lcn_kernels.h"
 #include "metrics_kernels.h"
 
 using namespace morl;
@@ -2617,6 +2618,36 @@ extern "C" int morl_pareto_mask(const double* points, int N, int R, int remove_d
         default: return fail(MORL_ERR_ARG, "R=%d", R);
     }
     LAUNCH_CHECK("pareto_mask");
+    return MORL_OK;
+}
+
+// ---- LCN's selection (lcn.py:221-252) ----------------------------------------------------------------------------------------
+static_assert(LCN_MAX_N == MORL_LCN_MAX_N, "the header states the kernel's limit");
+static_assert((2 * sizeof(float) * MORL_MAX_OBJ + 2 * sizeof(uint8_t) + 2 * sizeof(unsigned short)) * LCN_MAX_N + 2 * sizeof(int) <=
+                  160 * 1024,
+              "both row sets, the flags and the index lists fit one CU's LDS");
+
+extern "C" int morl_lcn_select(const float* returns, int N, int R, int mode, double lcn_lambda, const uint8_t* crowded,
+                               float* l2_out, uint8_t* nd_out, void* stream) {
+    if (!returns || !nd_out) return fail(MORL_ERR_ARG, "NULL array");
+    if ((crowded == nullptr) != (l2_out == nullptr))
+        return fail(MORL_ERR_ARG, "crowded and l2_out are NULL together (the mask-only form) or not at all");
+    if (N < 1 || N > LCN_MAX_N) return fail(MORL_ERR_ARG, "N=%d outside 1..%d", N, LCN_MAX_N);
+    if (R < 1 || R > MORL_MAX_OBJ) return fail(MORL_ERR_ARG, "R=%d outside 1..%d", R, MORL_MAX_OBJ);
+    if (mode < 0 || mode > 2) return fail(MORL_ERR_ARG, "mode=%d (0 Pareto, 1 Lorenz, 2 lambda-Lorenz)", mode);
+    if (mode == 2 && !std::isfinite(lcn_lambda)) return fail(MORL_ERR_ARG, "lcn_lambda is not finite");
+    // lcn.py:232: `lcn_lambda * returns` rounds lambda to float32, `(1 - lcn_lambda)` is a Python float rounded afterwards
+    const float lam = mode == 2 ? (float)lcn_lambda : 0.f, oml = mode == 2 ? (float)(1.0 - lcn_lambda) : 0.f;
+    const dim3 grid(1), block(LCN_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    switch (R) {
+#define MORL_LCN_CASE(r) case r: hipLaunchKernelGGL(lcn_select_kernel<r>, grid, block, 0, s, returns, N, mode, lam, oml, crowded, l2_out, nd_out); break;
+        MORL_LCN_CASE(1) MORL_LCN_CASE(2) MORL_LCN_CASE(3) MORL_LCN_CASE(4)
+        MORL_LCN_CASE(5) MORL_LCN_CASE(6) MORL_LCN_CASE(7) MORL_LCN_CASE(8)
+#undef MORL_LCN_CASE
+        default: return fail(MORL_ERR_ARG, "R=%d", R);
+    }
+    LAUNCH_CHECK("lcn_select");
     return MORL_OK;
 }
 

@@ -619,3 +619,13 @@ def sumtree_update(lib: NativeLib, tree: th.Tensor, n_levels: int, idx: th.Tenso
     lib.check_device(tree, idx, raw, running_max, pr_out)
     lib.check(lib.lib.morl_sumtree_update(_ptr(tree), n_levels, _ptr(idx), _ptr(raw), idx.numel(), float(alpha),
                                           _ptr(running_max), _ptr(pr_out), lib.stream_of(tree)))
+
+
+def sumtree_update_clamped(lib: NativeLib, tree: th.Tensor, n_levels: int, idx: th.Tensor, raw: th.Tensor, alpha: float,
+                           clamp_min: float, running_max: th.Tensor, pr_out: Optional[th.Tensor] = None) -> None:
+    """The GPI-PD form (``morl_sumtree_update_clamped``): priority = max(raw, clamp_min) ** alpha, alpha >= 0, clamp_min > 0."""
+    _chk(tree, th.float64, "tree"); _chk(idx, th.int64, "idx"); _chk(raw, th.float32, "raw")
+    _chk(running_max, th.float64, "running_max")
+    lib.check_device(tree, idx, raw, running_max, pr_out)
+    lib.check(lib.lib.morl_sumtree_update_clamped(_ptr(tree), n_levels, _ptr(idx), _ptr(raw), idx.numel(), float(alpha),
+                                                  float(clamp_min), _ptr(running_max), _ptr(pr_out), lib.stream_of(tree)))

@@ -2,7 +2,7 @@
 continuous) on one MI355X.  bench.py stays the north-star (Envelope) line the driver runs; this script measures the
 widened rows with the same conventions:
 
-    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn|lcn|ppo|nlppo|eupg [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench_ac.py --workload capql|mosac|morld|gpipd|gpi|ens|pcn|lcn|ipro|ppo|nlppo|eupg [--pop 64] [--steps K] [--warmup W] [--no-cpu-baseline]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench_ac.py --workload morld --gpus N --pop 64      # the population's learners are independent units: pop / N per
                                                                 # GPU, no data-path collective ("replicas only", weak scaling)
@@ -38,6 +38,7 @@ SHAPES = {  # obs dim, action dim, objectives of the environments BASELINE.json 
     "ens": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (GPI-PD Dyna model: one-hot action in, next-obs delta + reward out)"),
     "pcn": dict(D=9, Ad=4, R=2, env="treasure-line (discrete head) / mo-hopper-v4 shapes 11-3-3 (continuous head)"),
     "lcn": dict(D=9, Ad=4, R=3, env="heaps of 500 / 2048 episode returns in 3 / 8 objectives (LCN's selection)"),
+    "ipro": dict(D=0, Ad=0, R=4, env="fronts of 22 .. 100 points in 3 / 4 objectives, 33 / 50 lower points (IPRO's compute_hvis)"),
     "ppo": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
     "pgmorl": dict(D=17, Ad=6, R=2, env="mo-halfcheetah-v4"),
     "nlppo": dict(D=7, Ad=6, R=3, env="mo-minecart-v0 (NL-MO-PPO, discrete: 6 actions)"),
@@ -554,6 +555,105 @@ def bench_lcn(a):
            "roofline": {"bound": "latency", "kernel": "lcn_select_kernel", "achieved": None, "peak": None, "unit": None, "frac": None,
                         "traffic": None, "note": "one workgroup, N^2 pair tests on LDS broadcasts; the end-to-end call is two "
                                                  "uploads, a launch and a blocking read-back"}}
+    print(json.dumps(out), file=RESULT_OUT, flush=True)
+
+
+def bench_ipro(a):
+    """IPRO (multi_policy/ipro/ipro.py): one ``compute_hvis`` (ipro.py:212-226) -- the hypervolume of ``pf`` and ``completed`` plus
+    one lower point, for every drawn lower point -- as ONE ``morl_ipro_hvis`` call, timed end to end as ``IPRO.compute_hvis`` uses
+    it (one upload of base, candidates and reference, two launches, one read-back) and as the launches alone.  Next to it what the
+    package offered for the same scores before: K + 1 ``hypervolume_device`` calls in a loop, each with its upload (with one
+    read-back per call, as ``compute_hypervolume`` makes it, and with a single read-back at the end), and the float64 oracle
+    (tests/ipro_oracle.py) on this machine's host.  Every device result is checked against the oracle (1e-12) before anything is
+    timed.  The legs alternate, ``--steps`` calls per timed window, five windows each; the figure is the median window."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import ipro_oracle as io_
+    from morl_baselines_amd import performance_indicators as pi
+    from morl_baselines_amd.native import load_library
+
+    lib, dev = load_library(), th.device("cuda", 0)
+    loops = max(1, a.steps)
+    shapes = {}
+    for n, R, K in ((25, 3, 33), (22, 4, 50), (100, 3, 50), (60, 4, 50)):
+        tag = f"n{n}_r{R}_k{K}"
+        rng = np.random.default_rng(100 * n + R)
+        # a run's geometry: the base is a front of mutually non-dominated points, the candidates lie below it, ref is the ideal
+        v = np.abs(rng.standard_normal((n + K, R)))
+        v = 10.0 * v / np.linalg.norm(v, axis=1, keepdims=True)
+        ref = np.full(R, 11.0)
+        base, cand = 11.0 - v[:n], 11.0 - 1.3 * v[n:] * rng.uniform(0.6, 1.0, (K, 1))
+        want = np.asarray([io_.oracle_hv(np.vstack((base, c)), ref) for c in cand] + [io_.oracle_hv(base, ref)])
+        flat_d = th.from_numpy(np.concatenate([base.reshape(-1), cand.reshape(-1), ref])).to(dev)
+        base_d, cand_d, ref_d = flat_d[:n * R].view(n, R), flat_d[n * R:(n + K) * R].view(K, R), flat_d[(n + K) * R:]
+        sets = [np.concatenate([-np.vstack((base, c)).reshape(-1), -ref]) for c in cand] + [np.concatenate([-base.reshape(-1), -ref])]
+
+        def launch_only():
+            return pi.ipro_hvis_device(ref_d, base_d, cand_d, lib)
+
+        def end_to_end():
+            return pi.ipro_hvis(ref, base, cand, lib=lib, device=dev)
+
+        def one_hv(flat):
+            t = th.from_numpy(flat).to(dev)
+            rows = (flat.size - R) // R
+            return pi.hypervolume_device(t[rows * R:], t[:rows * R].view(rows, R), lib)
+
+        def loop_sync_each():
+            return np.asarray([float(one_hv(f).item()) for f in sets])
+
+        def loop_one_readback():
+            return th.stack([one_hv(f) for f in sets]).cpu().numpy()
+
+        def oracle_leg():
+            return [io_.oracle_hv(np.vstack((base, c)), ref) for c in cand] + [io_.oracle_hv(base, ref)]
+
+        worst = {}
+        for name, got in (("batched", end_to_end()), ("loop", loop_sync_each()), ("loop_one_readback", loop_one_readback())):
+            worst[name] = float(np.max(np.abs(got - want) / np.abs(want)))
+            if not worst[name] <= 1e-12:
+                raise SystemExit(f"bench_ac ipro {tag}: the {name} leg is {worst[name]:.3g} relative off the float64 oracle")
+        for _ in range(max(1, a.warmup)):
+            launch_only()
+            end_to_end()
+        loop_sync_each()
+        loop_one_readback()
+        th.cuda.synchronize()
+        legs = (("launch", launch_only, loops, True), ("end_to_end", end_to_end, loops, False),
+                ("loop", loop_sync_each, max(1, loops // 10), False), ("loop_one_readback", loop_one_readback, max(1, loops // 10), False),
+                ("oracle", oracle_leg, 1, False))
+        t = {name: [] for name, *_ in legs}
+        for window in range(5):
+            for name, fn, reps, sync in legs:
+                if name == "oracle" and window >= 2:        # (seconds per call at 60 points in 4 objectives: two windows of one call)
+                    continue
+                th.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    fn()
+                if sync:
+                    th.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) * 1e6 / reps)
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        shapes[tag] = {"shape": dict(n=n, R=R, K=K), "max_rel_error_vs_oracle": worst,
+                       "batched_end_to_end_us": med["end_to_end"], "batched_launches_only_us": med["launch"],
+                       "loop_of_hypervolume_device_us": med["loop"], "loop_one_readback_us": med["loop_one_readback"],
+                       "host_oracle_us": med["oracle"], "loop_over_batched": med["loop"] / med["end_to_end"],
+                       "loop_one_readback_over_batched": med["loop_one_readback"] / med["end_to_end"],
+                       "host_oracle_over_batched": med["oracle"] / med["end_to_end"], "windows_us": t,
+                       "calls_per_window": {name: reps for name, _, reps, _ in legs}}
+    d = shapes["n22_r4_k50"]
+    out = {"metric": "IPRO compute_hvis calls/sec (morl_ipro_hvis end to end: one upload, two launches, one read-back; n = 22, R = 4, K = 50)",
+           "value": 1e6 / d["batched_end_to_end_us"], "unit": "calls/s", "n_gpus": 1, "steps": loops, "warmup": a.warmup,
+           "ms_per_step": d["batched_end_to_end_us"] / 1e3, "higher_is_better": True, "vs_baseline": None, "dtype": "f64",
+           "data": "synthetic",
+           "config": {"workload": "IPRO.compute_hvis (ipro.py:212-226) at the shapes scripted runs reach and at larger fronts; "
+                                  "comparison: K + 1 separate hypervolume_device calls (the package before morl_ipro_hvis) and the "
+                                  "float64 oracle on this host"},
+           "shapes": shapes,
+           "roofline": {"bound": "latency", "kernel": "ipro_hvis_kernel", "achieved": None, "peak": None, "unit": None, "frac": None,
+                        "traffic": None, "note": "one workgroup per candidate on LDS-staged points; the end-to-end call is one "
+                                                 "upload, two launches and a blocking read-back"}}
     print(json.dumps(out), file=RESULT_OUT, flush=True)
 
 
@@ -1168,6 +1268,8 @@ def main():
         return bench_pcn(a)
     if a.workload == "lcn":
         return bench_lcn(a)
+    if a.workload == "ipro":
+        return bench_ipro(a)
     if a.workload == "ppo":
         return bench_ppo(a)
     if a.workload == "nlppo":

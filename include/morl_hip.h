@@ -469,6 +469,24 @@ int morl_hypervolume(const double* points, int N, int R, const double* ref_point
 int morl_expected_utility(const double* front, int N, int R, const double* weights, int M, double* workspace,
                           double* eum_out, void* stream);
 
+/* ---- IPRO's hypervolume improvements: multi_policy/ipro/ipro.py:212-226 (compute_hvis), :330-333 -------------------------
+ * The frame is OuterLoop.compute_hypervolume's (outer_loop.py:250-256), pymoo's minimisation frame without normalisation:
+ * a point p counts only if ref >= p in every coordinate and > in one (anything else is dropped, not clipped), and the value
+ * is the volume of the union of the boxes [p, ref].  All arrays are device float64: base [n][R], cand [K][R], ref [R],
+ * out [K + 1].  out[k] = hypervolume of base u {cand[k]} for k < K, out[K] = hypervolume of base alone; K = 0 and n = 0
+ * are allowed.  workspace: morl_ipro_hvis_workspace_doubles(n, K, R) doubles (-1 for a shape that is refused).
+ * Two launches whatever n and K are (a few workgroups per candidate beside the base's own -- how many depends on (n, R)
+ * only -- then the sums), nothing synchronises the host.  The bits of out[k] depend on (base, cand[k], ref) alone -- not
+ * on k, K or the grid -- so equal candidates tie.
+ * Limits: R 1..MORL_MAX_OBJ, n + 1 <= MORL_IPRO_MAX_POINTS (the LDS-staged size of the front metrics), K <= MORL_IPRO_MAX_K,
+ * (n + 1)^R <= 4e9 point tests for one candidate and (K + 1) (n + 1)^R <= 4e11 in all; anything else is refused before any
+ * launch. */
+#define MORL_IPRO_MAX_POINTS 512
+#define MORL_IPRO_MAX_K 1024
+int64_t morl_ipro_hvis_workspace_doubles(int n, int K, int R);
+int morl_ipro_hvis(const double* base, int n, const double* cand, int K, int R, const double* ref, double* workspace,
+                   double* out, void* stream);
+
 /* ---- PER sum-tree: common/prioritized_buffer.py:12-82 (device-resident) -------------------------
  * tree: device float64, levels concatenated root first; level l has 2^l nodes and starts at offset
  * 2^l - 1; n_levels = ceil(log2(capacity)) + 1.

@@ -27,6 +27,9 @@ def __getattr__(name):
     if name == "EUPG":
         from .eupg import EUPG
         return EUPG
+    if name in ("IPRO", "OuterLoop"):
+        from . import ipro
+        return getattr(ipro, name)
     if name == "PGMORL":
         from .pgmorl import PGMORL
         return PGMORL

@@ -33,6 +33,7 @@
 #include "pareto_kernels.h"
 #include "lcn_kernels.h"
 #include "metrics_kernels.h"
+#include "ipro_kernels.h"
 
 using namespace morl;
 
@@ -2684,6 +2685,48 @@ extern "C" int morl_hypervolume(const double* points, int N, int R, const double
     LAUNCH_CHECK("hv_boxes");
     hipLaunchKernelGGL(metric_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)part, blocks, 1.0, hv_out);
     LAUNCH_CHECK("hv_finish");
+    return MORL_OK;
+}
+
+// ---- IPRO's hypervolume improvements (multi_policy/ipro/ipro.py:212-226, 330-333) ------------------------------------------------
+static_assert(IPRO_MAX_N + 1 == MORL_IPRO_MAX_POINTS && IPRO_MAX_K == MORL_IPRO_MAX_K, "the header states the kernel's limits");
+static_assert(sizeof(double) * HV_MAX_N * (2 * MORL_MAX_OBJ - 1) + 64 <= 64 * 1024, "points and cuts fit the static LDS of a workgroup");
+
+// NULL when (n, K, R) is accepted, else what is wrong with it
+static const char* ipro_hvis_refusal(int n, int K, int R) {
+    if (R < 1 || R > MORL_MAX_OBJ) return "R outside 1..MORL_MAX_OBJ";
+    if (n < 0 || n > IPRO_MAX_N) return "n outside 0..MORL_IPRO_MAX_POINTS - 1";
+    if (K < 0 || K > IPRO_MAX_K) return "K outside 0..MORL_IPRO_MAX_K";
+    double tests = 1.0;                      // the uncompacted form's point tests per candidate: the kernel never needs more
+    for (int d = 0; d < R; ++d) tests *= (double)(n + 1);
+    if (tests > 4e9) return "more than 4e9 point tests for one candidate";
+    if (tests * (double)(K + 1) > 4e11) return "more than 4e11 point tests";
+    return nullptr;
+}
+
+extern "C" int64_t morl_ipro_hvis_workspace_doubles(int n, int K, int R) {
+    if (ipro_hvis_refusal(n, K, R)) return -1;
+    return (int64_t)K * IPRO_MAX_CAND_BLOCKS + IPRO_MAX_BASE_BLOCKS;
+}
+
+extern "C" int morl_ipro_hvis(const double* base, int n, const double* cand, int K, int R, const double* ref, double* workspace,
+                              double* out, void* stream) {
+    if (const char* why = ipro_hvis_refusal(n, K, R)) return fail(MORL_ERR_ARG, "ipro_hvis n=%d K=%d R=%d: %s", n, K, R, why);
+    if (!ref || !workspace || !out || (n > 0 && !base) || (K > 0 && !cand)) return fail(MORL_ERR_ARG, "NULL array");
+    hipStream_t s = (hipStream_t)stream;
+    const int shares = ipro_base_blocks(n, R), S = ipro_cand_blocks(n, R);
+    const dim3 grid(K * S + shares), block(IPRO_THREADS);
+    switch (R) {
+#define MORL_IPRO_CASE(r) case r: hipLaunchKernelGGL(ipro_hvis_kernel<r>, grid, block, 0, s, base, n, cand, K, S, ref, workspace); break;
+        MORL_IPRO_CASE(1) MORL_IPRO_CASE(2) MORL_IPRO_CASE(3) MORL_IPRO_CASE(4)
+        MORL_IPRO_CASE(5) MORL_IPRO_CASE(6) MORL_IPRO_CASE(7) MORL_IPRO_CASE(8)
+#undef MORL_IPRO_CASE
+        default: return fail(MORL_ERR_ARG, "R=%d", R);
+    }
+    LAUNCH_CHECK("ipro_hvis");
+    hipLaunchKernelGGL(ipro_finish_kernel, dim3((K + 1 + IPRO_THREADS - 1) / IPRO_THREADS), block, 0, s, (const double*)workspace, K,
+                       S, shares, out);
+    LAUNCH_CHECK("ipro_finish");
     return MORL_OK;
 }
 

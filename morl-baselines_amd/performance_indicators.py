@@ -63,7 +63,40 @@ def hypervolume(ref_point: np.ndarray, points: List[np.ndarray], lib: Optional[N
     return float(hypervolume_device(ref, pts, lib).item())
 
 
-def expected_utility(front: List[np.ndarray], weights_set: List[np.ndarray], utility: Callable = np.dot,
+def ipro_hvis_device(ref: th.Tensor, base: th.Tensor, cand: th.Tensor, lib: Optional[NativeLib] = None) -> th.Tensor:
+    """IPRO's batch of hypervolumes (``morl_ipro_hvis``; ``csrc/ipro_kernels.h``) in ``OuterLoop.compute_hypervolume``'s frame --
+    minimisation, ``ref`` the upper corner, a point that ``ref`` does not dominate is dropped.  ``base`` (n, R), ``cand`` (K, R)
+    and ``ref`` (R,) are device float64; returns a device float64 (K + 1,): the hypervolume of ``base`` with ``cand[k]`` added, for
+    every k, then that of ``base`` alone.  Two launches whatever n and K are, no sync."""
+    lib = lib or load_library()
+    (n, R), K = base.shape, cand.shape[0]
+    words = int(lib.lib.morl_ipro_hvis_workspace_doubles(n, K, R))
+    ws = th.empty(max(words, 1), dtype=th.float64, device=ref.device)
+    out = th.empty(K + 1, dtype=th.float64, device=ref.device)
+    lib.check_device(base, cand, ref)
+    for t, name in ((base, "base"), (cand, "cand"), (ref, "ref")):
+        if t.dtype != th.float64 or not t.is_contiguous():
+            raise TypeError(f"ipro_hvis_device: {name} must be a contiguous float64 tensor")
+    lib.check(lib.lib.morl_ipro_hvis(base.data_ptr() if n else None, n, cand.data_ptr() if K else None, K, R, ref.data_ptr(),
+                                     ws.data_ptr(), out.data_ptr(), lib.stream_of(out)))
+    return out
+
+
+def ipro_hvis(ref: np.ndarray, base: np.ndarray, cand: np.ndarray, lib: Optional[NativeLib] = None, device=None) -> np.ndarray:
+    """``ipro_hvis_device`` for host arrays: ONE upload of ``base | cand | ref``, the launches, one read-back of K + 1 doubles."""
+    lib = lib or load_library()
+    dev = _dev(lib, device)
+    ref = np.asarray(ref, dtype=np.float64).reshape(-1)
+    R = ref.shape[0]
+    base = np.asarray(base, dtype=np.float64).reshape(-1, R)
+    cand = np.asarray(cand, dtype=np.float64).reshape(-1, R)
+    n, K = base.shape[0], cand.shape[0]
+    flat = th.from_numpy(np.concatenate([base.reshape(-1), cand.reshape(-1), ref])).to(dev)
+    out = ipro_hvis_device(flat[(n + K) * R:], flat[:n * R].view(n, R), flat[n * R:(n + K) * R].view(K, R), lib)
+    return out.cpu().numpy()
+
+
+def expected_utility(front: List[np.ndarray],weights_set: List[np.ndarray], utility: Callable = np.dot,
                      lib: Optional[NativeLib] = None, device=None) -> float:
     """``performance_indicators.py:71-91``.  The dot-product utility runs on the device; any other utility is evaluated
     with the reference's host loop."""

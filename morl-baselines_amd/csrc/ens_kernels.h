@@ -10,6 +10,9 @@ __device__ __forceinline__ float ens_softplus(float x) {       // F.softplus: be
     return x > 20.f ? x : log1pf(expf(x));
 }
 __device__ __forceinline__ float ens_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+// 1 - sigmoid(x) = sigmoid(-x) next to s = ens_sigmoid(x): for x > 0 from the exponential itself (e / (1 + e), e = exp(-x) <= 1),
+// where 1.f - s cancels -- at the initial bounds lv1 - min is about 10, s = 1 - 2.7e-5, and the subtraction keeps three digits
+__device__ __forceinline__ float ens_sigmoid_comp(float x, float s) { return x > 0.f ? expf(-x) * s : 1.f - s; }
 
 // input normalisation h = (x - mu) / sigma into the members' input rows (probabilistic_ensemble.py:92-95)
 struct EnsNormArgs {
@@ -38,12 +41,19 @@ __global__ __launch_bounds__(256) void ens_norm_kernel(EnsNormArgs a) {
 }
 
 // bounded log-variance of the raw head output (probabilistic_ensemble.py:112-114)
-__device__ __forceinline__ float ens_bound(float raw, float mx, float mn, float& s_max, float& s_min) {
+__device__ __forceinline__ float ens_bound(float raw, float mx, float mn, float& s_max, float& s_min, float& c_max,
+                                           float& c_min) {
     const float lv1 = mx - ens_softplus(mx - raw);
-    s_max = ens_sigmoid(mx - raw);          // d lv1 / d raw        (and 1 - s_max = d lv1 / d max)
+    s_max = ens_sigmoid(mx - raw);          // d lv1 / d raw
+    c_max = ens_sigmoid_comp(mx - raw, s_max);      // 1 - s_max = d lv1 / d max
     const float lv = mn + ens_softplus(lv1 - mn);
-    s_min = ens_sigmoid(lv1 - mn);          // d lv / d lv1         (and 1 - s_min = d lv / d min)
+    s_min = ens_sigmoid(lv1 - mn);          // d lv / d lv1
+    c_min = ens_sigmoid_comp(lv1 - mn, s_min);      // 1 - s_min = d lv / d min
     return lv;
+}
+__device__ __forceinline__ float ens_bound(float raw, float mx, float mn, float& s_max, float& s_min) {
+    float c_max, c_min;
+    return ens_bound(raw, mx, mn, s_max, s_min, c_max, c_min);
 }
 
 // Gaussian NLL (F.gaussian_nll_loss, full = False, eps 1e-6, reduction none -> mean over E * rows * out) + its
@@ -81,19 +91,22 @@ __global__ __launch_bounds__(256) void ens_nll_kernel(EnsNllArgs a) {
             const int o = lane + 64 * j;
             if (o < a.O) {
                 const float mean = hd[o], raw = hd[a.O + o];
-                float s_max, s_min;
-                const float lv = ens_bound(raw, a.bounds[o], a.bounds[a.O + o], s_max, s_min);
+                float s_max, s_min, c_max, c_min;
+                const float lv = ens_bound(raw, a.bounds[o], a.bounds[a.O + o], s_max, s_min, c_max, c_min);
                 const float var = expf(lv);
                 const float vc = fmaxf(var, 1e-6f);                  // gaussian_nll_loss clamps the variance
                 const float d = mean - y[o];
                 loss += 0.5 * ((double)logf(vc) + (double)(d * d / vc));
                 const float dmean = a.inv_count * d / vc;
-                // d/dvar of 0.5 (log var + d^2 / var) = 0.5 (1 / var - d^2 / var^2); var = exp(lv) -> times var (0 if clamped)
-                const float dlv = (var > 1e-6f) ? a.inv_count * 0.5f * (1.f - d * d / vc) : 0.f;
+                // d/dvar of 0.5 (log vc + d^2 / vc) = 0.5 (1 / vc - d^2 / vc^2); var = exp(lv) -> times var.  torch clamps the
+                // variance in place under no_grad, so the gradient passes straight through the clamp: the factor var / vc
+                // stays (exactly 1 where var > eps; the unclamped branch is kept as it was, bit for bit)
+                const float dlv0 = a.inv_count * 0.5f * (1.f - d * d / vc);
+                const float dlv = (var > 1e-6f) ? dlv0 : dlv0 * (var / vc);
                 dh[o] = dmean;
                 dh[a.O + o] = dlv * s_min * s_max;
-                dmx[j] = dlv * s_min * (1.f - s_max);
-                dmn[j] = dlv * (1.f - s_min);
+                dmx[j] = dlv * s_min * c_max;
+                dmn[j] = dlv * c_min;
             }
         }
         for (int c = 2 * a.O + lane; c < a.ld; c += 64) dh[c] = 0.f;

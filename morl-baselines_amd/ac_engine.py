@@ -14,6 +14,7 @@ import numpy as np
 import torch as th
 
 from . import native
+from .acnets import flat_views
 from .native import GRAD_HOOK, ACBatch, ACCfg, ACDesc, ACOut, ACState, NativeLib
 
 ALGO_CAPQL, ALGO_MOSAC, ALGO_TD3, ALGO_SACD = 0, 1, 2, 3
@@ -46,13 +47,9 @@ class ACEngine:
         self.heads = 1 if algo in (ALGO_TD3, ALGO_SACD) else 2
         self.w_input = algo not in (ALGO_MOSAC, ALGO_SACD)
         self.discrete = algo == ALGO_SACD            # act_dim = number of actions; critics output A * R values
-        self.Pq = int(self.lib.lib.morl_ac_q_param_count(C.byref(d)))
-        self.Pp = int(self.lib.lib.morl_ac_policy_param_count(C.byref(d)))
-        if self.Pq < 0 or self.Pp < 0:
-            self.lib.check(-1)
-        h = C.c_void_p()
-        self.lib.check(self.lib.lib.morl_ac_create(C.byref(h), C.byref(d)))
-        self._h = h.value
+        self.Pq = self.lib.family_param_count("ac_q", C.byref(d))
+        self.Pp = self.lib.family_param_count("ac_policy", C.byref(d))
+        self._h = native.Context(self.lib, "ac", C.byref(d))
         self._ctor = dict(algo=algo, obs_dim=obs_dim, act_dim=act_dim, reward_dim=reward_dim, net_arch=list(net_arch),
                           action_low=action_low, action_high=action_high, max_rows=max_rows, num_q=num_q,
                           q_layer_norm=q_layer_norm, q_drop_rate=q_drop_rate, device=device, lib=self.lib)
@@ -90,14 +87,6 @@ class ACEngine:
         algo, D, Ad, R, arch = (kw.pop(k_) for k_ in ("algo", "obs_dim", "act_dim", "reward_dim", "net_arch"))
         return ACEngine(algo, D, Ad, R, arch, population=1, state=state, **kw)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self.lib.lib.morl_ac_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
     # -- parameter views (torch nn.Sequential.parameters() order) ---------------------------------------------------
     def _q_shapes(self):
         out, d = [], (self.D if self.discrete else self.D + self.Ad + (self.R if self.w_input else 0))
@@ -109,15 +98,7 @@ class ACEngine:
         n_out = self.Ad * self.R if self.discrete else self.R
         return out + [(n_out, d), (n_out,)]
 
-    @staticmethod
-    def _views(flat: th.Tensor, shapes) -> List[th.Tensor]:
-        out, o = [], 0
-        for s in shapes:
-            n = int(np.prod(s))
-            out.append(flat[o:o + n].view(s))
-            o += n
-        assert o == flat.numel(), (o, flat.numel())
-        return out
+    _views = staticmethod(flat_views)
 
     def q_views(self, buf: th.Tensor, p: int = 0, n: int = 0) -> List[th.Tensor]:
         """Views of critic ``n`` of learner ``p`` inside ``buf`` (self.q, self.q_target, an Adam moment buffer)."""

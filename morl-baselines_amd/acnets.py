@@ -9,6 +9,7 @@ from __future__ import annotations
 
 from typing import List, Sequence
 
+import math
 import os
 
 import numpy as np
@@ -86,13 +87,48 @@ def bind(module: nn.Module, views: Sequence[th.Tensor], copy_in: bool = True) ->
             p.requires_grad_(False)
 
 
-def adam_state_dict(params_views, m_views, v_views, step: int, lr: float) -> dict:
+def flat_views(flat: th.Tensor, shapes) -> List[th.Tensor]:
+    """Cut the 1-D ``flat`` into consecutive views of ``shapes``; the shapes must consume it exactly."""
+    sizes = [math.prod(s) for s in shapes]
+    if flat.dim() != 1 or sum(sizes) != flat.numel():
+        raise ValueError(f"shapes of {sum(sizes)} elements do not match a flat buffer of {tuple(flat.shape)}")
+    out, o = [], 0
+    for s, n in zip(shapes, sizes):
+        out.append(flat[o:o + n].view(tuple(s)))
+        o += n
+    return out
+
+
+def bind_flat(module: nn.Module, flat: th.Tensor, copy_in: bool = True) -> None:
+    """``bind`` the module to ``flat`` cut by its own ``parameters()``: the module's layout must be the library's flat layout."""
+    bind(module, flat_views(flat, [p.shape for p in module.parameters()]), copy_in)
+
+
+class FlatAdam:
+    """What a fused-step learner's ``self.optimizer`` is used for from outside: ``param_groups[0]`` (``lr``, ``betas``, ``eps``),
+    ``state_dict()`` / ``load_state_dict()`` in torch.optim.Adam's layout over the learner's flat buffers; plus the step count."""
+
+    def __init__(self, lr: float, eps: float, shapes, params: th.Tensor, exp_avg: th.Tensor, exp_avg_sq: th.Tensor):
+        self.param_groups = [{"lr": lr, "betas": (0.9, 0.999), "eps": eps}]
+        self.steps = 0
+        self._shapes, self._flat = [tuple(s) for s in shapes], (params, exp_avg, exp_avg_sq)
+
+    def state_dict(self) -> dict:
+        g = self.param_groups[0]
+        return adam_state_dict(*(flat_views(t, self._shapes) for t in self._flat), self.steps, g["lr"], g["eps"])
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.param_groups[0]["lr"] = sd["param_groups"][0]["lr"]
+        self.steps = load_adam_state_dict(sd, *(flat_views(t, self._shapes) for t in self._flat[1:]))
+
+
+def adam_state_dict(params_views, m_views, v_views, step: int, lr: float, eps: float = 1e-8) -> dict:
     """torch.optim.Adam.state_dict() layout built from the flat moment buffers (so reference code can load it)."""
     state = {}
     if step > 0:
         for i, (m, v) in enumerate(zip(m_views, v_views)):
             state[i] = {"step": th.tensor(float(step)), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
-    group = {"lr": lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0, "amsgrad": False, "maximize": False,
+    group = {"lr": lr, "betas": (0.9, 0.999), "eps": eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
              "foreach": None, "capturable": False, "differentiable": False, "fused": None,
              "params": list(range(len(params_views)))}
     return {"state": state, "param_groups": [group]}

@@ -45,12 +45,8 @@ class ProbabilisticEnsemble(nn.Module):
         for i, h in enumerate(arch):
             d.hidden[i] = int(h)
         self.desc, self.max_rows, self._O = d, max_rows, output_dim
-        self.Pm = int(self.lib.lib.morl_ens_param_count(C.byref(d)))
-        if self.Pm < 0:
-            self.lib.check(-1)
-        h = C.c_void_p()
-        self.lib.check(self.lib.lib.morl_ens_create(C.byref(h), C.byref(d)))
-        self._h = h.value
+        self.Pm = self.lib.family_param_count("ens", C.byref(d))
+        self._h = native.Context(self.lib, "ens", C.byref(d))
         E = ensemble_size
         z = lambda *s: th.zeros(*s, dtype=th.float32, device=self.device)  # noqa: E731
         self.flat, self.exp_avg, self.exp_avg_sq = z(E, self.Pm), z(E, self.Pm), z(E, self.Pm)
@@ -67,14 +63,6 @@ class ProbabilisticEnsemble(nn.Module):
         self.inputs_sigma = th.zeros((1, input_dim), device=self.device)
         self._adam_step = 0
         self.lib.check_device(self.flat)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self.lib.lib.morl_ens_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     # -- parameter views ------------------------------------------------------------------------------------------------
     def _layer_views(self, buf: th.Tensor):

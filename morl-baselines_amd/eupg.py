@@ -16,7 +16,6 @@ freshly initialised network and steps an orphaned one).
 """
 from __future__ import annotations
 
-import ctypes as C
 import time
 from copy import deepcopy
 from typing import Callable, List, Optional, Union
@@ -26,9 +25,9 @@ import torch as th
 from torch import nn
 from torch.distributions import Categorical
 
-from .acnets import adam_state_dict, bind
+from .acnets import FlatAdam, bind_flat
 from .api import MOAgent, MOPolicy
-from .native import NativeLib, load_library
+from .native import Context, NativeLib, load_library
 
 MAX_HIDDEN = 128
 
@@ -89,31 +88,6 @@ class EpisodeBuffer:
         return self.size
 
 
-class _Optimizer:
-    """What ``self.optimizer`` is used for from outside: ``param_groups[0]["lr"]``, ``state_dict()``; plus the Adam step count."""
-
-    def __init__(self, owner: "EUPG", lr: float):
-        self.owner, self.steps = owner, 0
-        self.param_groups = [{"lr": lr, "betas": (0.9, 0.999), "eps": 1e-8}]
-
-    def state_dict(self) -> dict:
-        o = self.owner
-        return adam_state_dict(o._views(o.params), o._views(o.exp_avg), o._views(o.exp_avg_sq), self.steps, self.param_groups[0]["lr"])
-
-    def load_state_dict(self, sd: dict) -> None:
-        o = self.owner
-        self.param_groups[0]["lr"] = sd["param_groups"][0]["lr"]
-        o.exp_avg.zero_()
-        o.exp_avg_sq.zero_()
-        self.steps = 0
-        for i, (m, v) in enumerate(zip(o._views(o.exp_avg), o._views(o.exp_avg_sq))):
-            if i in sd["state"]:
-                st = sd["state"][i]
-                m.copy_(st["exp_avg"].to(m.device))
-                v.copy_(st["exp_avg_sq"].to(v.device))
-                self.steps = int(st["step"])
-
-
 class EUPG(MOPolicy, MOAgent):
     """Expected Utility Policy Gradient (Roijers, Steckelmacher & Nowe, 2018) -- the constructor, ``train``, ``update``, ``eval``,
     ``get_save_dict`` / ``load``, ``get_config`` and ``__deepcopy__`` of the reference class (``eupg.py:78-398``)."""
@@ -150,39 +124,21 @@ class EUPG(MOPolicy, MOAgent):
         arch = self.net_arch
         self._shape = (int(self.observation_shape[0]), int(self.action_dim), int(self.reward_dim), len(arch), arch[0],
                        arch[1] if len(arch) > 1 else 0)
-        P = int(self.lib.lib.morl_eupg_param_count(*self._shape))
-        if P < 0:
-            raise ValueError(self.lib.lib.morl_last_error().decode())
+        P = self.lib.family_param_count("eupg", *self._shape, error=ValueError)
         self.params = th.zeros(P, dtype=th.float32, device=self.device)
         self.exp_avg = th.zeros_like(self.params)
         self.exp_avg_sq = th.zeros_like(self.params)
-        views = self._views(self.params)
-        assert sum(v.numel() for v in views) == P, "PolicyNet.parameters() does not match the library's flat layout"
-        bind(self.net, views)
-        self.optimizer = _Optimizer(self, self.learning_rate)
+        bind_flat(self.net, self.params)
+        self.optimizer = FlatAdam(self.learning_rate, 1e-8, [p.shape for p in self.net.parameters()], self.params, self.exp_avg,
+                                  self.exp_avg_sq)
         self._reserve(1024)
         self.last_loss = None                  # 0-dim device tensor of the last update()
         self.last_scalarized_return = None     # scalarization(episodic return, weights) of the last update()
         self.last_returns = None               # [T][R] device tensor: the discounted returns of the last update()
 
-    def __del__(self):
-        self._destroy()
-
     def _destroy(self):
-        ctx, self._ctx = getattr(self, "_ctx", None), None
-        if ctx:
-            try:
-                self.lib.lib.morl_eupg_destroy(ctx)
-            except Exception:       # interpreter shutdown: the library handle may already be gone
-                pass
-
-    def _views(self, flat: th.Tensor):
-        views, o = [], 0
-        for p in self.net.parameters():
-            n = p.numel()
-            views.append(flat[o:o + n].view(*p.shape))
-            o += n
-        return views
+        if self._ctx:
+            self._ctx.close()
 
     def _reserve(self, rows: int):
         """A context whose table holds an episode of ``rows`` steps (episodes have no length limit in the reference)."""
@@ -190,9 +146,7 @@ class EUPG(MOPolicy, MOAgent):
             return
         self._destroy()
         rows = max(rows, 2 * self._max_rows)
-        h = C.c_void_p()
-        self.lib.check(self.lib.lib.morl_eupg_create(C.byref(h), *self._shape, rows, 0))
-        self._ctx, self._max_rows = h.value, rows
+        self._ctx, self._max_rows = Context(self.lib, "eupg", *self._shape, rows, 0), rows
 
     # -- the device side -------------------------------------------------------------------------------------------------
     def _probs(self, obs, acc_reward) -> th.Tensor:

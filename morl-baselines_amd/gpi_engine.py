@@ -8,6 +8,7 @@ import numpy as np
 import torch as th
 
 from . import native
+from .acnets import flat_views
 from .native import GPIBatch, GPICfg, GPIDesc, GPIOut, GPIPer, NativeLib
 
 
@@ -29,23 +30,11 @@ class GPIEngine:
         self.D, self.A, self.R, self.arch = obs_dim, n_actions, reward_dim, [int(h) for h in net_arch]
         self.num_nets, self.layer_norm, self.drop_rate = num_nets, bool(layer_norm), float(drop_rate)
         self.max_rows, self.max_support = max_rows, max_support
-        self.P = int(self.lib.lib.morl_gpi_param_count(C.byref(d)))
-        if self.P < 0:
-            self.lib.check(-1)
-        h = C.c_void_p()
-        self.lib.check(self.lib.lib.morl_gpi_create(C.byref(h), C.byref(d)))
-        self._h = h.value
+        self.P = self.lib.family_param_count("gpi", C.byref(d))
+        self._h = native.Context(self.lib, "gpi", C.byref(d))
         z = lambda: th.zeros((num_nets, self.P), dtype=th.float32, device=self.device)  # noqa: E731
         self.q, self.q_target, self.exp_avg, self.exp_avg_sq = z(), z(), z(), z()
         self.lib.check_device(self.q)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self.lib.lib.morl_gpi_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     def shapes(self):
         """``QNet.parameters()`` order: weights_features, state_features, net."""
@@ -59,13 +48,7 @@ class GPIEngine:
         return out + [(self.A * self.R, d), (self.A * self.R,)]
 
     def views(self, buf: th.Tensor, n: int) -> List[th.Tensor]:
-        out, o = [], 0
-        for s in self.shapes():
-            k = int(np.prod(s))
-            out.append(buf[n, o:o + k].view(s))
-            o += k
-        assert o == self.P
-        return out
+        return flat_views(buf[n], self.shapes())
 
     def _f32(self, t) -> th.Tensor:
         t = th.as_tensor(t)

@@ -14,17 +14,16 @@ Not here: ``make_env`` and its gymnasium wrappers (``envs`` is any object with `
 """
 from __future__ import annotations
 
-import ctypes as C
 from copy import deepcopy
-from typing import List, Optional, Union
+from typing import Callable, List, Optional, Union
 
 import numpy as np
 import torch as th
 from torch import nn
 
-from .acnets import bind
+from .acnets import FlatAdam, bind_flat
 from .api import MOPolicy
-from .native import NativeLib, load_library
+from .native import Context, NativeLib, _ptr, load_library
 
 SUPPORTED_HIDDEN = (32, 64, 96, 128)
 STAT_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "grad_norm")
@@ -89,12 +88,40 @@ class PPOReplayBuffer:
         return (self.obs, self.actions, self.logprobs, self.rewards, self.dones, self.values)
 
 
-class _Optimizer:
-    """What the reference's ``self.optimizer`` is used for from outside: ``param_groups[0]["lr"]``; plus the Adam step count."""
+def epoch_steps(rng: np.random.Generator, b_inds: np.ndarray, minibatch_size: int) -> list:
+    """One epoch of the reference's loop: shuffle ``b_inds`` in place, cut it into minibatches (copies; the last may be shorter)."""
+    rng.shuffle(b_inds)
+    return [b_inds[s:s + minibatch_size].copy() for s in range(0, len(b_inds), minibatch_size)]
 
-    def __init__(self, lr: float):
-        self.param_groups = [{"lr": lr, "betas": (0.9, 0.999), "eps": 1e-5}]
-        self.steps = 0
+
+def by_size(groups: list, steps: list) -> list:
+    """Consecutive minibatches of one size form a call (a batch that ``num_minibatches`` does not divide ends every epoch with
+    a shorter one, as in the reference: a call takes steps of one size)."""
+    for mb in steps:
+        if groups and len(groups[-1][-1]) == len(mb):
+            groups[-1].append(mb)
+        else:
+            groups.append([mb])
+    return groups
+
+
+def run_epochs(rng: np.random.Generator, batch_size: int, minibatch_size: int, epochs: int, target_kl: Optional[float],
+               update_n: Callable[[np.ndarray], th.Tensor]) -> th.Tensor:
+    """The PPO learners' epoch schedule: the shuffles are drawn from ``rng`` call for call as the reference draws them and the
+    steps of all epochs go to ``update_n(idx [n][M]) -> stats [n][8]`` in one call per run of equal-sized minibatches
+    (``target_kl``: the calls of one epoch, then one read of its last ``approx_kl``, which may end the loop).  Returns the
+    statistics of every step, concatenated."""
+    b_inds = np.arange(batch_size)
+    calls, stats = [], []
+    for _ in range(epochs):
+        by_size(calls, epoch_steps(rng, b_inds, minibatch_size))
+        if target_kl is not None:
+            stats += [update_n(np.stack(c)) for c in calls]
+            calls = []
+            if float(stats[-1][-1, STAT_NAMES.index("approx_kl")]) > target_kl:
+                break
+    stats += [update_n(np.stack(c)) for c in calls]
+    return stats[0] if len(stats) == 1 else th.cat(stats)
 
 
 class MOPPO(MOPolicy):
@@ -139,41 +166,21 @@ class MOPPO(MOPolicy):
         if len(np.asarray(weights).reshape(-1)) != R or np.asarray(weights).dtype != np.float32:
             raise ValueError(f"MOPPO: weights must be {R} float32 entries (they multiply float32 advantages, mo_ppo.py:475)")
         shape = (D, A, R, len(arch), arch[0], arch[1] if len(arch) > 1 else 0)
-        P = int(self.lib.lib.morl_ppo_param_count(*shape))
-        if P < 0:
-            raise ValueError(self.lib.lib.morl_last_error().decode())
-        h = C.c_void_p()
-        self.lib.check(self.lib.lib.morl_ppo_create(C.byref(h), *shape, self.minibatch_size))
-        self._ctx = h.value
+        P = self.lib.family_param_count("ppo", *shape, error=ValueError)
+        self._ctx = Context(self.lib, "ppo", *shape, self.minibatch_size)
         self._dims = (D, A, R)
         self.params = th.zeros(P, dtype=th.float32, device=self.device)
         self.exp_avg = th.zeros_like(self.params)
         self.exp_avg_sq = th.zeros_like(self.params)
-        self._bind_networks()
-        self.optimizer = _Optimizer(self.learning_rate)
+        bind_flat(self.networks, self.params)
+        self.optimizer = FlatAdam(self.learning_rate, 1e-5, [p.shape for p in networks.parameters()], self.params, self.exp_avg,
+                                  self.exp_avg_sq)
         self.last_stats = None           # [steps][8] device tensor of the last update(): STAT_NAMES per step
 
         self.batch = PPOReplayBuffer(self.steps_per_iteration, self.num_envs, networks.obs_shape, networks.action_shape, R,
                                      self.device)
 
-    def __del__(self):
-        ctx, self._ctx = getattr(self, "_ctx", None), None
-        if ctx:
-            try:
-                self.lib.lib.morl_ppo_destroy(ctx)
-            except Exception:       # interpreter shutdown: the library handle may already be gone
-                pass
-
     # -- parameters ----------------------------------------------------------------------------------------------------
-    def _bind_networks(self):
-        views, o = [], 0
-        for p in self.networks.parameters():
-            n = p.numel()
-            views.append(self.params[o:o + n].view(*p.shape))
-            o += n
-        assert o == self.params.numel(), "MOPPONet.parameters() does not match the library's flat layout"
-        bind(self.networks, views)
-
     def __deepcopy__(self, memo):
         """``mo_ppo.py:343-376``: a copy of the networks and the rollout behind a context, parameter vector and (fresh, as in the
         reference) optimiser state of its own."""
@@ -204,9 +211,8 @@ class MOPPO(MOPolicy):
             action = th.empty(rows, A, dtype=th.float32, device=self.device)
             logprob = th.empty(rows, dtype=th.float32, device=self.device)
         self.lib.check_device(self.params, obs, value, eps_d)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self.lib.check(self.lib.lib.morl_ppo_forward(self._ctx, self.params.data_ptr(), obs.data_ptr(), ptr(eps_d), rows,
-                                                     int(eps is None), ptr(action), ptr(logprob), value.data_ptr(),
+        self.lib.check(self.lib.lib.morl_ppo_forward(self._ctx, self.params.data_ptr(), obs.data_ptr(), _ptr(eps_d), rows,
+                                                     int(eps is None), _ptr(action), _ptr(logprob), value.data_ptr(),
                                                      self.lib.stream_of(value)))
         return action, logprob, value
 
@@ -273,25 +279,8 @@ class MOPPO(MOPolicy):
         """``mo_ppo.py:492-558``.  The rollout, its returns and advantages are the ones the last ``_compute_advantages`` put into
         the context's table.  The shuffles are drawn from ``np_random`` call for call; the steps of all epochs go to the device
         in one ``morl_ppo_update_n`` call (``target_kl``: one call per epoch, and one read of the epoch's last ``approx_kl``)."""
-        b_inds = np.arange(self.batch_size)
-        calls, stats = [], []
-        for _ in range(self.update_epochs):
-            self.np_random.shuffle(b_inds)
-            steps = [b_inds[s:s + self.minibatch_size].copy() for s in range(0, self.batch_size, self.minibatch_size)]
-            # (a batch that num_minibatches does not divide ends every epoch with a shorter minibatch, as in the reference: a
-            # call takes steps of one size)
-            for mb in steps:
-                if calls and len(calls[-1][-1]) == len(mb):
-                    calls[-1].append(mb)
-                else:
-                    calls.append([mb])
-            if self.target_kl is not None:
-                stats += [self._update_n(np.stack(c)) for c in calls]
-                calls = []
-                if float(stats[-1][-1, STAT_NAMES.index("approx_kl")]) > self.target_kl:
-                    break
-        stats += [self._update_n(np.stack(c)) for c in calls]
-        self.last_stats = stats[0] if len(stats) == 1 else th.cat(stats)
+        self.last_stats = run_epochs(self.np_random, self.batch_size, self.minibatch_size, self.update_epochs, self.target_kl,
+                                     self._update_n)
 
     def train(self, start_time, current_iteration: int, max_iterations: int):
         """``mo_ppo.py:576-608``: one iteration of ``steps_per_iteration * num_envs`` environment steps and one ``update()``."""

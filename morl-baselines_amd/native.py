@@ -313,6 +313,49 @@ def _ptr(t: Optional[th.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+class Context:
+    """The one owner of a ``morl_<family>_create`` context (``ppo``, ``nlppo``, ``eupg``, ``pcn``, ``ac``, ``gpi``, ``ens``).
+
+    Pass it wherever a ``morl_*`` entry takes the context: ``_as_parameter_`` is the raw pointer while the context is open and
+    None (NULL: the library's own "NULL argument" error, not a freed pointer) once it is closed.  It refuses ``copy``, ``deepcopy``
+    and ``pickle``: a copied integer would be destroyed twice, so whoever owns a context re-creates it for its twin."""
+
+    def __init__(self, lib: "NativeLib", family: str, *args):
+        self._lib, self.family, self._as_parameter_ = lib, family, None
+        h = C.c_void_p()
+        lib.check(getattr(lib.lib, f"morl_{family}_create")(C.byref(h), *args))
+        self._as_parameter_ = h.value
+
+    @property
+    def value(self) -> Optional[int]:
+        return self._as_parameter_
+
+    def __bool__(self) -> bool:
+        return self._as_parameter_ is not None
+
+    def __eq__(self, other) -> bool:       # (by pointer: two owners of one context must compare equal)
+        return isinstance(other, Context) and self.value == other.value
+
+    def close(self) -> bool:
+        """Destroy the context; False if it was closed already."""
+        h, self._as_parameter_ = self._as_parameter_, None
+        if h is None:
+            return False
+        getattr(self._lib.lib, f"morl_{self.family}_destroy")(h)
+        return True
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown: the library handle may already be gone
+            pass
+
+    def _refuse_copy(self, *_):
+        raise TypeError(f"a morl_{self.family} context cannot be copied or pickled: its owner creates a new one")
+
+    __copy__ = __deepcopy__ = __reduce_ex__ = _refuse_copy
+
+
 def _chk(t: th.Tensor, dtype, name: str) -> th.Tensor:
     if t.dtype != dtype:
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
@@ -337,6 +380,11 @@ class NativeLib:
         if self.lib.morl_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI version {self.lib.morl_abi_version()} != {ABI_VERSION}")
         self.is_device_build = bool(self.lib.morl_is_device_build())
+
+    def __deepcopy__(self, memo):
+        # (the generic deepcopy of an owner gets here or to its Context first; an owner that can be copied has a __deepcopy__
+        # that hands ``lib`` to its twin)
+        raise TypeError("a loaded libmorl_hip cannot be copied: the owner's __deepcopy__ passes it on to the twin it builds")
 
     # -- helpers --------------------------------------------------------------------------------
     def check(self, rc: int) -> None:
@@ -374,6 +422,16 @@ class NativeLib:
 
     def param_count(self, desc: NetDesc) -> int:
         return int(self.lib.morl_param_count(C.byref(desc)))
+
+    def family_param_count(self, family: str, *args, error=None) -> int:
+        """``morl_<family>_param_count(*args)``.  A refused shape raises ``error`` with the library's message (the learners pass
+        ``ValueError``), or what ``check`` raises."""
+        n = int(getattr(self.lib, f"morl_{family}_param_count")(*args))
+        if n < 0 and error is not None:
+            raise error(self.lib.morl_last_error().decode())
+        if n < 0:
+            self.check(-1)
+        return n
 
 
 def make_net_desc(obs_dim: int, reward_dim: int, n_actions: int, net_arch: Sequence[int]) -> NetDesc:

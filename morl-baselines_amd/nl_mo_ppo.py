@@ -21,7 +21,6 @@ Not here: W&B logging, and ``envs`` is any object with ``num_envs``, ``single_ob
 """
 from __future__ import annotations
 
-import ctypes as C
 from math import ceil
 from typing import Callable, Optional, Sequence, Union
 
@@ -30,10 +29,10 @@ import torch as th
 from torch import nn
 from torch.distributions.categorical import Categorical
 
-from .acnets import bind
+from .acnets import FlatAdam, bind_flat
 from .api import MOPolicy
-from .mo_ppo import STAT_NAMES, SUPPORTED_HIDDEN, _Optimizer
-from .native import NativeLib, load_library
+from .mo_ppo import STAT_NAMES, SUPPORTED_HIDDEN, run_epochs
+from .native import Context, NativeLib, _ptr, load_library
 
 
 def _layer_init(layer: nn.Linear, std: float = np.sqrt(2), bias_const: float = 0.0) -> nn.Linear:
@@ -119,16 +118,9 @@ class NLMOPPO(MOPolicy):
         self.reset_agent(pref_dim=self.num_objectives)
         self._setup_storage()
 
-    def __del__(self):
-        self._destroy()
-
     def _destroy(self):
-        ctx, self._ctx = getattr(self, "_ctx", None), None
-        if ctx:
-            try:
-                self.lib.lib.morl_nlppo_destroy(ctx)
-            except Exception:       # interpreter shutdown: the library handle may already be gone
-                pass
+        if self._ctx:
+            self._ctx.close()
 
     def reset_agent(self, pref_dim: int):
         """``nl_mo_ppo.py:219-224``: a freshly initialised agent (and context) for ``pref_dim``, zero Adam state, no utility."""
@@ -137,24 +129,15 @@ class NLMOPPO(MOPolicy):
         arch = self.net_arch
         shape = (self.agent.obs_dim, self.agent.n_actions, self.num_objectives, int(pref_dim), len(arch), arch[0],
                  arch[1] if len(arch) > 1 else 0)
-        P = int(self.lib.lib.morl_nlppo_param_count(*shape))
-        if P < 0:
-            raise ValueError(self.lib.lib.morl_last_error().decode())
-        h = C.c_void_p()
-        self.lib.check(self.lib.lib.morl_nlppo_create(C.byref(h), *shape, self.minibatch_size))
-        self._ctx = h.value
+        P = self.lib.family_param_count("nlppo", *shape, error=ValueError)
+        self._ctx = Context(self.lib, "nlppo", *shape, self.minibatch_size)
         self._dims = (self.agent.obs_dim, self.agent.n_actions, self.num_objectives, int(pref_dim))
         self.params = th.zeros(P, dtype=th.float32, device=self.device)
         self.exp_avg = th.zeros_like(self.params)
         self.exp_avg_sq = th.zeros_like(self.params)
-        views, o = [], 0
-        for p in self.agent.parameters():
-            n = p.numel()
-            views.append(self.params[o:o + n].view(*p.shape))
-            o += n
-        assert o == P, "Agent.parameters() does not match the library's flat layout"
-        bind(self.agent, views)
-        self.optimizer = _Optimizer(self.learning_rate)
+        bind_flat(self.agent, self.params)
+        self.optimizer = FlatAdam(self.learning_rate, 1e-5, [p.shape for p in self.agent.parameters()], self.params, self.exp_avg,
+                                  self.exp_avg_sq)
         self.u_func = None
         self.pref = None
 
@@ -186,9 +169,8 @@ class NLMOPPO(MOPolicy):
         value = th.empty(rows, R, dtype=th.float32, device=self.device)
         logp = None if value_only else th.empty(rows, A, dtype=th.float32, device=self.device)
         self.lib.check_device(self.params, obs, acc, pref_d, value)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self.lib.check(self.lib.lib.morl_nlppo_forward(self._ctx, self.params.data_ptr(), obs.data_ptr(), acc.data_ptr(), ptr(pref_d),
-                                                       rows, int(value_only), ptr(logp), value.data_ptr(), self.lib.stream_of(value)))
+        self.lib.check(self.lib.lib.morl_nlppo_forward(self._ctx, self.params.data_ptr(), obs.data_ptr(), acc.data_ptr(), _ptr(pref_d),
+                                                       rows, int(value_only), _ptr(logp), value.data_ptr(), self.lib.stream_of(value)))
         return logp, value
 
     def _sample(self, obs, acc_reward, pref):
@@ -277,26 +259,9 @@ class NLMOPPO(MOPolicy):
         loss_weights = self._compute_loss_weights()
         self.last_loss_weights = loss_weights
         w_dev = loss_weights.to(self.device, th.float32).contiguous()
-        b_inds = np.arange(self.batch_size)
-        calls, stats = [], []
-        for _ in range(self.update_epochs):
-            self.rng.shuffle(b_inds)
-            steps = [b_inds[s:s + self.minibatch_size].copy() for s in range(0, self.batch_size, self.minibatch_size)]
-            # (a batch that num_minibatches does not divide ends every epoch with a shorter minibatch, as in the reference: a
-            # call takes steps of one size)
-            for mb in steps:
-                if calls and len(calls[-1][-1]) == len(mb):
-                    calls[-1].append(mb)
-                else:
-                    calls.append([mb])
-            if self.target_kl is not None:
-                stats += [self._update_n(np.stack(c), w_dev) for c in calls]
-                calls = []
-                if float(stats[-1][-1, STAT_NAMES.index("approx_kl")]) > self.target_kl:
-                    break
-        stats += [self._update_n(np.stack(c), w_dev) for c in calls]
+        self.last_stats = run_epochs(self.rng, self.batch_size, self.minibatch_size, self.update_epochs, self.target_kl,
+                                     lambda idx: self._update_n(idx, w_dev))
         self._keep_w = w_dev
-        self.last_stats = stats[0] if len(stats) == 1 else th.cat(stats)
         host = self.last_stats.cpu()
         last = host[-1]
         clipfrac = float(np.mean([float(c) for c in host[:, STAT_NAMES.index("clipfrac")]]))

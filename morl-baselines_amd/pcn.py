@@ -18,14 +18,13 @@ import os
 from dataclasses import dataclass
 from typing import List, Optional, Type, Union
 
-import ctypes as C
 import numpy as np
 import torch as th
 from torch import nn
 
-from .acnets import bind
+from .acnets import bind, flat_views
 from .api import MOAgent, MOPolicy
-from .native import NativeLib, load_library
+from .native import Context, NativeLib, load_library
 from .pareto import get_non_dominated_inds
 
 SUPPORTED_HIDDEN = (32, 64, 96, 128)
@@ -109,12 +108,8 @@ class PCN(MOAgent, MOPolicy):
         D, A, R, H = int(self.observation_dim), int(self.action_dim), int(self.reward_dim), int(hidden_dim)
         if len(np.asarray(scaling_factor).reshape(-1)) != R + 1:
             raise ValueError(f"scaling_factor needs reward_dim + 1 = {R + 1} entries")
-        P = int(self.lib.lib.morl_pcn_param_count(D, R, A, H))
-        if P < 0:
-            raise ValueError(self.lib.lib.morl_last_error().decode())
-        h = C.c_void_p()
-        self.lib.check(self.lib.lib.morl_pcn_create(C.byref(h), D, R, A, H, int(self.continuous_action), int(batch_size)))
-        self._ctx = h.value
+        P = self.lib.family_param_count("pcn", D, R, A, H, error=ValueError)
+        self._ctx = Context(self.lib, "pcn", D, R, A, H, int(self.continuous_action), int(batch_size))
         self._dims = (D, R, A, H)
         self.params = th.zeros(P, dtype=th.float32, device=self.device)
         self.exp_avg = th.zeros_like(self.params)
@@ -130,24 +125,10 @@ class PCN(MOAgent, MOPolicy):
             experiment_name += " continuous action" if self.continuous_action else ""
             self.setup_wandb(project_name, experiment_name, wandb_entity)
 
-    def __del__(self):
-        ctx, self._ctx = getattr(self, "_ctx", None), None
-        if ctx:
-            try:
-                self.lib.lib.morl_pcn_destroy(ctx)
-            except Exception:       # interpreter shutdown: the library handle may already be gone
-                pass
-
     # -- parameters ----------------------------------------------------------------------------------------------------
     def _views(self, flat: th.Tensor):
         D, R, A, H = self._dims
-        shapes = [(H, D), (H,), (H, R + 1), (H,), (H, H), (H,), (A, H), (A,)]
-        out, o = [], 0
-        for s in shapes:
-            n = int(np.prod(s))
-            out.append(flat[o:o + n].view(*s))
-            o += n
-        return out
+        return flat_views(flat, [(H, D), (H,), (H, R + 1), (H,), (H, H), (H,), (A, H), (A,)])
 
     def _bind_model(self):
         bind(self.model, [self.model.scaling_factor.detach().to(self.device)] + self._views(self.params))

@@ -43,7 +43,7 @@ import torch as th
 from scipy.optimize import least_squares
 
 from .api import MOAgent
-from .mo_ppo import MOPPO, MOPPONet, STAT_NAMES
+from .mo_ppo import MOPPO, MOPPONet, STAT_NAMES, by_size, epoch_steps
 from .native import NativeLib, load_library
 from .pareto import ParetoArchive
 from .performance_indicators import hypervolume, sparsity
@@ -237,7 +237,7 @@ def _ptrs(tensors):
 
 
 def _handles(agents):
-    return (C.c_void_p * len(agents))(*[a._ctx for a in agents])
+    return (C.c_void_p * len(agents))(*[a._ctx.value for a in agents])
 
 
 def population_forward(lib: NativeLib, agents: List[MOPPO], obs: th.Tensor, eps: Optional[th.Tensor]):
@@ -347,22 +347,6 @@ def train_population(lib: NativeLib, agents: List[MOPPO], current_iteration: int
     return global_step
 
 
-def _epoch_steps(a: MOPPO, b_inds: np.ndarray):
-    a.np_random.shuffle(b_inds)
-    return [b_inds[s:s + a.minibatch_size].copy() for s in range(0, a.batch_size, a.minibatch_size)]
-
-
-def _by_size(groups: list, steps: list) -> list:
-    """Consecutive minibatches of one size form a call (a batch that ``num_minibatches`` does not divide ends every epoch with
-    a shorter one), as in ``MOPPO.update``."""
-    for mb in steps:
-        if groups and len(groups[-1][-1]) == len(mb):
-            groups[-1].append(mb)
-        else:
-            groups.append([mb])
-    return groups
-
-
 def update_population(lib: NativeLib, agents: List[MOPPO]):
     """``MOPPO.update()`` of every agent, in agent order, as population calls (see the module docstring)."""
     a0 = agents[0]
@@ -371,7 +355,7 @@ def update_population(lib: NativeLib, agents: List[MOPPO]):
         for a in agents:                                   # agent 0's epochs, then agent 1's: the generators' order of use
             b_inds, g = np.arange(a.batch_size), []
             for _ in range(a.update_epochs):
-                _by_size(g, _epoch_steps(a, b_inds))
+                by_size(g, epoch_steps(a.np_random, b_inds, a.minibatch_size))
             groups.append(g)
         stats = [[] for _ in agents]
         for k in range(len(groups[0])):
@@ -389,7 +373,7 @@ def update_population(lib: NativeLib, agents: List[MOPPO]):
     stats = [[] for _ in agents]
     active = list(range(len(agents)))
     for _ in range(a0.update_epochs):
-        groups = [_by_size([], _epoch_steps(agents[i], b_inds[i])) for i in active]
+        groups = [by_size([], epoch_steps(agents[i].np_random, b_inds[i], agents[i].minibatch_size)) for i in active]
         act = [agents[i] for i in active]
         for k in range(len(groups[0])):
             for i, new in zip(active, population_update_n(lib, act, [np.stack(g[k]) for g in groups])):
